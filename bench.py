@@ -14,7 +14,14 @@ N=1 workload is BASELINE config 2 (the largest single-GPU config): 100M-row
 lineitem, lz4, stripe 150k / chunk group 10k (reference defaults). N>1:
 per-rank shards of the same size (weak scaling; config-3 shape).
 
+A plain run does only what the headline figure needs: setup, warmup, the
+timed steps, the result line. --full adds the legs that take runs of their
+own: the in-run parity pin (expected aggregates recomputed on host from the
+seeded generator) and the CPU baselines (oracle, single-thread + all-core).
+--dump-outputs DIR writes what the last timed step returned as .npy files.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R]
+                       [--full] [--dump-outputs DIR]
 Multi-GPU via: python -m torch.distributed.run --nnodes=1 --nproc-per-node N
                --master-addr 127.0.0.1 bench.py --gpus N ...
 """
@@ -70,6 +77,38 @@ def count_preds(ca):
     return [(1, ca.PRED_LT, 2400)]    # l_quantity < 24 (config 1)
 
 
+def dump_outputs(out_dir, result, group_cols):
+    """Write the combined aggregates the last timed step returned.
+
+    aggregates.npy: float64 [n_groups, n_aggs, 8] (n_groups = 1 ungrouped),
+    columns = i128 as a double, its four 32-bit two's-complement limbs (most
+    significant first; exact where the double is not), count, f64, is_null.
+    group_keys.npy (grouped only): float64 [n_groups, 2], NaN = NULL key;
+    rows follow the sorted key order used in aggregates.npy.
+    """
+    import numpy as np
+
+    def rows(parts):
+        out = []
+        for p in parts:
+            u = p.i128 & ((1 << 128) - 1)
+            limbs = [(u >> s) & 0xFFFFFFFF for s in (96, 64, 32, 0)]
+            out.append([float(p.i128)] + [float(x) for x in limbs] +
+                       [float(p.count), float(p.f64), float(p.is_null)])
+        return out
+
+    os.makedirs(out_dir, exist_ok=True)
+    if group_cols:
+        keys = sorted(result, key=lambda k: tuple(-1 if x is None else x for x in k))
+        np.save(os.path.join(out_dir, "group_keys.npy"),
+                np.array([[float("nan") if x is None else float(x) for x in k]
+                          for k in keys], dtype=np.float64).reshape(len(keys), -1))
+        agg = [rows(result[k]) for k in keys]
+    else:
+        agg = [rows(result)]
+    np.save(os.path.join(out_dir, "aggregates.npy"), np.array(agg, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,7 +131,14 @@ def main():
                     help="shard files per GPU scanned as one table (config 3: "
                          "4 shards/GPU x 8 GPUs = 32 shards). 0 = auto: 16 for "
                          ">=100M rows (parallel generation), else 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the in-run parity pin and the CPU baselines "
+                         "(off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's combined aggregates to "
+                         "DIR/aggregates.npy (+ DIR/group_keys.npy when grouped)")
     args = ap.parse_args()
 
     build_if_needed()
@@ -231,6 +277,9 @@ def main():
             td.destroy_process_group()
         return
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result, group_cols)
+
     total_rows = args.rows * world
     value = total_rows * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
@@ -270,7 +319,7 @@ def main():
     # independent end-to-end check of writer -> stage -> decode -> filter ->
     # aggregate -> combine at the FULL benchmark size.
     parity = None
-    if rank == 0:
+    if args.full:
         # expected values cover EVERY rank's shards (seeds are deterministic:
         # rank r uses base 42 + r*shards), so the pin also holds for the
         # multi-GPU combined result
@@ -312,7 +361,7 @@ def main():
     # ---- CPU baseline (oracle restatement, rank 0, N=1 only) ----
     cpu_baseline = None
     cpu_mt = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         import oracle
         # bounded sample: ONE shard file of the same dataset (~10-30 s CPU)
         if args.shards > 1:
@@ -385,7 +434,7 @@ def main():
             "kernel": dominant,
         },
         "cpu_baseline": cpu_baseline,
-        "cpu_baseline_allcore": cpu_mt if (world == 1 and not args.no_cpu_baseline) else None,
+        "cpu_baseline_allcore": cpu_mt,
     }
     print(json.dumps(out))
 

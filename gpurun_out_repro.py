@@ -1,5 +1,5 @@
-import numpy as np, sys
-sys.path.insert(0, "/root/repo")
+import numpy as np, os, sys
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import citus_amd as ca, oracle
 
 def chk(name, cond):

@@ -1,7 +1,7 @@
 """Perf probe: gen N-row lineitem, stage, run Q6 scan_agg 3x and print
 per-pass kernel ms (used for on-hardware A/B iterations this round)."""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import citus_amd as ca
 
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 30_000_000
