@@ -95,6 +95,13 @@ class Batch(C.Structure):
                 ("col_nulls", C.POINTER(C.POINTER(C.c_uint8)))]
 
 
+class Rows(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64),
+                ("col_values", C.POINTER(C.c_void_p)),
+                ("col_nulls", C.POINTER(C.c_void_p)),
+                ("row_numbers", C.c_void_p)]
+
+
 class GroupResult(C.Structure):
     _fields_ = [("n_groups", C.c_uint32), ("keys", C.c_uint32 * 64)]
 
@@ -156,6 +163,13 @@ _next_batch = _sig("cstripe_scan_next_batch", C.c_int, [C.c_void_p, C.POINTER(Ba
 _read_row = _sig("cstripe_read_row", C.c_int,
                  [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p),
                   C.POINTER(C.c_uint8)])
+_select_count = _sig("cstripe_scan_select_count", C.c_int,
+                     [C.c_void_p, C.POINTER(C.c_uint64)])
+_select = _sig("cstripe_scan_select", C.c_int,
+               [C.c_void_p, C.POINTER(Rows), C.c_uint64, C.c_int])
+_last_select_ms = _sig("cstripe_scan_last_select_ms", C.c_int,
+                       [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                        C.POINTER(C.c_double)])
 _rewind = _sig("cstripe_scan_rewind", C.c_int, [C.c_void_p])
 _last_fused = _sig("cstripe_scan_last_fused", C.c_int, [C.c_void_p])
 _last_kernel_ms = _sig("cstripe_scan_last_kernel_ms", C.c_double, [C.c_void_p])
@@ -437,6 +451,7 @@ class Scan:
             self._mask |= 1 << p[0]
         if self._mask == 0:
             self._mask = 1
+        self._device = -1
 
     def end(self):
         if self._h:
@@ -475,6 +490,7 @@ class Scan:
 
     def stage(self, device=-1):
         _check(_gpu_stage(self._h, device), "gpu_stage")
+        self._device = device
 
     def agg(self, aggs):
         """aggs: list of (kind, col_a[, col_b[, col_c[, one]]]) -> [Partial]"""
@@ -539,6 +555,100 @@ class Scan:
         _check(rc, "read_row")
         return {c: (None if nulls[c] else bufs[c][0].item())
                 for c in bufs}
+
+    def select_count(self):
+        """Rows select() returns: runs the device predicate pass and keeps
+        the pass mask on the scan for a following select()."""
+        n = C.c_uint64()
+        _check(_select_count(self._h, C.byref(n)), "scan_select_count")
+        return n.value
+
+    @property
+    def last_select_ms(self):
+        """(mask, offsets, emit) device ms of the last select/select_count"""
+        m, o, e = C.c_double(), C.c_double(), C.c_double()
+        _check(_last_select_ms(self._h, C.byref(m), C.byref(o), C.byref(e)),
+               "scan_last_select_ms")
+        return m.value, o.value, e.value
+
+    def select(self, cols=None, want_nulls=True, want_row_numbers=True,
+               device=False):
+        """Filtered row materialisation (cstripe_scan_select): the rows that
+        pass the scan's predicates, compacted on device, in scan order.
+        cols: column indices to return (None = every projected column).
+        Returns {"n_rows", "row_numbers", "values": {col: array},
+        "nulls": {col: array}}; row_numbers / nulls are None / {} when not
+        wanted. Host mode returns numpy arrays (read_row's dtype map);
+        device=True returns torch tensors on the scan's device (ints and
+        floats by width, TEXT as int32 bit patterns, row numbers int64)
+        whose data_ptr() can go straight into write_table_device."""
+        r = self._reader
+        ncols = r.column_count
+        if cols is None:
+            cols = [c for c in range(ncols) if (self._mask >> c) & 1]
+        cols = list(cols)
+        for c in cols:
+            if not 0 <= c < ncols:
+                raise CStripeError(f"select: column {c} out of range")
+        types = {c: r.column_def(c)[1] for c in cols}
+        n = self.select_count()
+        m_ms, o_ms, _ = self.last_select_ms
+        d_ms = self.last_decode_ms
+        cap = max(n, 1)
+        if device:
+            import torch
+            dev = torch.device("cuda", self._device if self._device >= 0
+                               else torch.cuda.current_device())
+            DT = {1: torch.int8, 2: torch.int16, 3: torch.int32,
+                  4: torch.int64, 5: torch.float32, 6: torch.float64,
+                  7: torch.int32}
+
+            def alloc(dt):
+                return torch.empty(cap, dtype=dt, device=dev)
+
+            def ptr(a):
+                return a.data_ptr()
+            null_dt, rn_dt = torch.uint8, torch.int64
+            torch.cuda.synchronize(dev)
+        else:
+            import numpy as np
+            DT = {1: np.int8, 2: np.int16, 3: np.int32, 4: np.int64,
+                  5: np.float32, 6: np.float64, 7: np.uint32}
+
+            def alloc(dt):
+                return np.zeros(cap, dtype=dt)
+
+            def ptr(a):
+                return a.ctypes.data_as(C.c_void_p).value
+            null_dt, rn_dt = np.uint8, np.int64
+        vals = {c: alloc(DT[types[c]]) for c in cols}
+        nulls = {c: alloc(null_dt) for c in cols} if want_nulls else {}
+        rn = alloc(rn_dt) if want_row_numbers else None
+        rows = Rows()
+        vp = (C.c_void_p * ncols)()
+        for c, a in vals.items():
+            vp[c] = ptr(a)
+        rows.col_values = vp
+        if want_nulls:
+            np_ = (C.c_void_p * ncols)()
+            for c, a in nulls.items():
+                np_[c] = ptr(a)
+            rows.col_nulls = np_
+        if rn is not None:
+            rows.row_numbers = ptr(rn)
+        _check(_select(self._h, C.byref(rows), cap, 1 if device else 0),
+               "scan_select")
+        k = rows.n_rows
+        # device time of this call, both ABI calls together
+        e_ms = self.last_select_ms[2]
+        d_ms += self.last_decode_ms
+        self.select_profile = {"decode_ms": d_ms, "mask_ms": m_ms,
+                               "offsets_ms": o_ms, "emit_ms": e_ms,
+                               "total_ms": d_ms + m_ms + o_ms + e_ms}
+        return {"n_rows": k,
+                "row_numbers": None if rn is None else rn[:k],
+                "values": {c: a[:k] for c, a in vals.items()},
+                "nulls": {c: a[:k] for c, a in nulls.items()}}
 
     def rewind(self):
         _check(_rewind(self._h), "rewind")

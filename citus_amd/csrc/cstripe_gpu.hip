@@ -136,6 +136,19 @@ struct cs_gpu_state {
     std::vector<uint8_t> col_scratch;/* per proj: any chunk lands in scratch */
     int *d_error = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    /* scan_select (filtered row materialisation): per-tile pass masks,
+     * counts and output bases, cached once computed — predicates are fixed
+     * at scan_begin, so only scan_end / restage drops them */
+    uint64_t *d_sel_mask = nullptr;     /* [tiles][64] pass words, 1 bit/row */
+    uint32_t *d_sel_counts = nullptr;   /* [tiles] passing rows */
+    uint64_t *d_sel_bases = nullptr;    /* [tiles] exclusive scan of counts */
+    uint64_t *d_sel_total = nullptr;    /* one word: rows that passed */
+    uint64_t *d_sel_rowbase = nullptr;  /* [groups] table-wide first row */
+    uint8_t *d_sel_out = nullptr;       /* host-mode compaction buffer */
+    uint64_t sel_out_bytes = 0;
+    bool sel_cached = false;
+    uint64_t sel_total = 0;
+    hipEvent_t sev[4] = {nullptr, nullptr, nullptr, nullptr};
 
     uint64_t data_bytes = 0;
     uint64_t scratch_bytes = 0;
@@ -3028,6 +3041,13 @@ void csgpu_release(cstripe_scan *s)
     if (g->d_tiles) HIP_DROP(hipFree(g->d_tiles));
     if (g->d_tiles2) HIP_DROP(hipFree(g->d_tiles2));
     if (g->d_error) HIP_DROP(hipFree(g->d_error));
+    if (g->d_sel_mask) HIP_DROP(hipFree(g->d_sel_mask));
+    if (g->d_sel_counts) HIP_DROP(hipFree(g->d_sel_counts));
+    if (g->d_sel_bases) HIP_DROP(hipFree(g->d_sel_bases));
+    if (g->d_sel_total) HIP_DROP(hipFree(g->d_sel_total));
+    if (g->d_sel_rowbase) HIP_DROP(hipFree(g->d_sel_rowbase));
+    if (g->d_sel_out) HIP_DROP(hipFree(g->d_sel_out));
+    for (hipEvent_t e : g->sev) if (e) HIP_DROP(hipEventDestroy(e));
     if (g->ev0) HIP_DROP(hipEventDestroy(g->ev0));
     if (g->ev1) HIP_DROP(hipEventDestroy(g->ev1));
     if (g->ev2) HIP_DROP(hipEventDestroy(g->ev2));
@@ -4270,6 +4290,565 @@ int csgpu_next_batch(cstripe_scan *s, cstripe_batch *batch)
     int rc = csgpu_fetch_batch(s, (uint32_t)s->batch_pos, batch);
     if (rc == CSTRIPE_OK) s->batch_pos++;
     return rc;
+}
+
+/* =====================================================================
+ * scan_select — device-side filtered row materialisation: the qual loop of
+ * ColumnarScanNext (columnar_customscan.c:1854-1913: read a row, ExecQual,
+ * return the rows that pass) with the rows themselves coming out, not an
+ * aggregate of them. Deterministic three-kernel compaction, no global
+ * atomics, same grid as the aggregate kernels (one block per chunk group x
+ * TILE_ROWS tile, 4 waves of 64):
+ *   select_mask_kernel    CNF per row -> __ballot pass word per 64-row
+ *                         slice (1 bit/row) + one u32 count per tile
+ *   select_offsets_kernel exclusive scan of the tile counts -> u64 bases,
+ *                         grand total to one device word
+ *   select_emit_kernel    rank inside the tile from the mask words, gather
+ *                         the wanted columns through col_value, store value /
+ *                         null byte / row number at base + rank
+ * Output order is scan order (ascending row number) by construction.
+ * ===================================================================== */
+
+#define SEL_SLICES (TILE_ROWS / WAVE)      /* mask words per tile */
+#define SEL_SCAN_ITEMS 8                   /* counts per thread per pass */
+#define SEL_UNROLL 4                       /* mask slices in flight per wave */
+
+struct SelCol {
+    uint8_t *vals;          /* destination, physical width per row */
+    uint8_t *nulls;         /* destination null bytes, or nullptr */
+    uint32_t proj;
+    uint32_t pad;
+};
+
+struct SelectParams {
+    uint32_t n_cols, tiles_per_group;
+    uint64_t *row_numbers;  /* destination, or nullptr */
+    SelCol cols[MAX_PROJ];
+};
+
+/* A dense width-8 column chunk whose value j sits at a closed-form byte
+ * position — raw or scratch-decoded typed arrays, canonical LIT / CONST /
+ * P(L) for both codecs (the same positions col_value computes):
+ *   value(j) = (load8(base + pos(j)) & keep) | high,
+ *   pos(j)   = j == 0 ? p0 : j == 1 ? p1 : a * j + b
+ * so the mask pass can issue its loads with no branch between them. */
+struct SelFast {
+    const uint8_t *base;
+    uint64_t keep, high;
+    uint32_t p0, p1, a, b;
+    bool f64;
+};
+
+__device__ inline bool sel_fast_setup(const uint8_t *__restrict__ data,
+                                      const uint8_t *__restrict__ scratch,
+                                      const ColLoc &cl, SelFast &f)
+{
+    f.base = (cl.flags & 1) ? scratch + cl.val_off : data + cl.val_off;
+    f.keep = ~0ull; f.high = 0;
+    f.p0 = 0; f.p1 = 8; f.a = 8; f.b = 0;
+    f.f64 = cl.type == CSTRIPE_F64;
+    if (!(cl.flags & 2) || cl.width != 8) return false;
+    if (!(cl.flags & 4)) return true;               /* typed array */
+    const uint32_t L = cl.L;
+    if (cl.mode == CSF_SEGMODE_LIT) {
+        f.base += (uint64_t)cl.hval;                /* skip literal-run header */
+        return true;
+    }
+    if (cl.mode == CSF_SEGMODE_CONST || cl.mode == CSF_SEGMODE_ZR_CONST) {
+        f.keep = 0; f.high = (uint64_t)cl.hval;
+        f.p1 = 0; f.a = 0;                          /* every row reads pos 0 */
+        return true;
+    }
+    if (cl.mode > CSF_SEGMODE_P_BASE && cl.mode <= CSF_SEGMODE_P_BASE + 4) {
+        f.p0 = 1; f.p1 = 9; f.a = L + 3; f.b = 6 - L;       /* canon_pos, lz4 */
+    } else if (cl.mode > CSF_SEGMODE_ZRP_BASE && cl.mode <= CSF_SEGMODE_ZRP_BASE + 4) {
+        f.p0 = 15; f.p1 = 23; f.a = L; f.b = 23 - L;        /* canon_pos, zstd */
+    } else {
+        return false;
+    }
+    if (L < 1 || L > 4) return false;
+    f.keep = (~0ull) >> ((8u - L) * 8u);
+    f.high = (uint64_t)cl.hval;
+    return true;
+}
+
+template <int NPREDS>
+__global__ __launch_bounds__(AGG_BLOCK) void select_mask_kernel(
+    const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
+    const uint32_t *__restrict__ rank, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, uint64_t *__restrict__ mask,
+    uint32_t *__restrict__ counts, const AggParams params)
+{
+    const uint32_t n_preds = NPREDS >= 0 ? (uint32_t)NPREDS : params.n_preds;
+    constexpr int UNROLL_PREDS = NPREDS > 0 ? NPREDS : 1;
+    const uint32_t gid = blockIdx.x / params.tiles_per_group;
+    const uint32_t tile = blockIdx.x % params.tiles_per_group;
+    const GroupDesc g = groups[gid];
+    const ColLoc *cols = colloc + g.colbase;
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+
+    /* slices of this tile that hold rows; the rest of the 64 words are 0 */
+    const uint32_t rc = g.row_count;
+    const uint32_t t0 = tile * TILE_ROWS;
+    const uint32_t n_sl = rc > t0 ? min((rc - t0 + WAVE - 1) / WAVE, (uint32_t)SEL_SLICES) : 0u;
+
+    /* dense width-8 predicate columns in a closed-form layout (SelFast):
+     * block-uniform, and only for the compile-time predicate counts */
+    SelFast fast[UNROLL_PREDS];
+    bool all_fast = NPREDS > 0;
+    if (NPREDS > 0) {
+        #pragma unroll
+        for (int p = 0; p < UNROLL_PREDS; p++)
+            all_fast = all_fast & sel_fast_setup(data, scratch,
+                                                 cols[params.preds[p].proj], fast[p]);
+    }
+
+    uint32_t wcount = 0;
+    /* each wave takes SEL_UNROLL consecutive slices per trip. Rows past
+     * row_count are clamped to the chunk's last row and masked out, so no
+     * load sits behind a per-row branch. */
+    for (uint32_t sl0 = wid * SEL_UNROLL; sl0 < n_sl;
+         sl0 += (AGG_BLOCK / WAVE) * SEL_UNROLL) {
+        bool pass[SEL_UNROLL];
+        if (all_fast) {
+            /* one unaligned 8 B load per (slice, predicate), all issued
+             * back to back before the first compare; predicates on the
+             * same column re-load the same address (a cache hit) to keep
+             * the sequence straight-line */
+            uint64_t raw[SEL_UNROLL][UNROLL_PREDS];
+            #pragma unroll
+            for (uint32_t u = 0; u < SEL_UNROLL; u++) {
+                const uint32_t rrow = min(t0 + (sl0 + u) * WAVE + lane, rc - 1);
+                #pragma unroll
+                for (int p = 0; p < UNROLL_PREDS; p++) {
+                    const SelFast &f = fast[p];
+                    const uint32_t pos = rrow < 2 ? (rrow == 0 ? f.p0 : f.p1)
+                                                  : f.a * rrow + f.b;
+                    __builtin_memcpy(&raw[u][p], f.base + pos, 8);
+                }
+            }
+            #pragma unroll
+            for (uint32_t u = 0; u < SEL_UNROLL; u++) {
+                bool ps = t0 + (sl0 + u) * WAVE + lane < rc, gv = false;
+                #pragma unroll
+                for (int p = 0; p < UNROLL_PREDS; p++) {
+                    const PredD &pr = params.preds[p];
+                    const uint64_t r = (raw[u][p] & fast[p].keep) | fast[p].high;
+                    const int64_t iv = (int64_t)r;
+                    double fv;
+                    if (fast[p].f64) __builtin_memcpy(&fv, &r, 8);
+                    else fv = (double)iv;
+                    gv = gv | pred_eval(pr, iv, fv);
+                    if (pr.gend) { ps = ps & gv; gv = false; }
+                }
+                pass[u] = ps;
+            }
+        } else {
+            #pragma unroll
+            for (uint32_t u = 0; u < SEL_UNROLL; u++) {
+                const uint32_t row = t0 + (sl0 + u) * WAVE + lane;
+                const uint32_t rrow = min(row, rc - 1);  /* n_sl > 0 => rc >= 1 */
+                bool ps = row < rc, gv = false;
+                int last_proj = -1;
+                int64_t liv = 0; double lfv = 0; bool lok = false;
+                /* same OR-group fold as filter_agg_kernel */
+                #pragma unroll UNROLL_PREDS
+                for (uint32_t p = 0; p < n_preds; p++) {
+                    const PredD &pr = params.preds[p];
+                    if ((int)pr.proj != last_proj) {
+                        lok = col_value(data, scratch, rank, cols[pr.proj], rrow, liv, lfv);
+                        last_proj = (int)pr.proj;
+                    }
+                    gv = gv | (lok && pred_eval(pr, liv, lfv));
+                    if (pr.gend) { ps = ps & gv; gv = false; }
+                }
+                pass[u] = ps;
+            }
+        }
+        #pragma unroll
+        for (uint32_t u = 0; u < SEL_UNROLL; u++) {
+            const uint32_t sl = sl0 + u;
+            if (sl >= n_sl) break;                      /* wave-uniform */
+            const uint64_t word = __ballot(pass[u]);
+            if (lane == 0) mask[(uint64_t)blockIdx.x * SEL_SLICES + sl] = word;
+            wcount += (uint32_t)__popcll(word);
+        }
+    }
+    for (uint32_t sl = n_sl + threadIdx.x; sl < SEL_SLICES; sl += AGG_BLOCK)
+        mask[(uint64_t)blockIdx.x * SEL_SLICES + sl] = 0;
+
+    __shared__ uint32_t lds[AGG_BLOCK / WAVE];
+    if (lane == 0) lds[wid] = wcount;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t w = 0; w < AGG_BLOCK / WAVE; w++) c += lds[w];
+        counts[blockIdx.x] = c;
+    }
+}
+
+/* one block: exclusive scan of n tile counts. Each pass covers
+ * AGG_BLOCK * SEL_SCAN_ITEMS entries (thread-serial over its items, wave
+ * shuffle scan, LDS across the 4 waves) with a u64 running carry. */
+__global__ __launch_bounds__(AGG_BLOCK) void select_offsets_kernel(
+    const uint32_t *__restrict__ counts, uint64_t *__restrict__ bases,
+    uint64_t *__restrict__ total, uint32_t n)
+{
+    __shared__ uint32_t wsum[AGG_BLOCK / WAVE];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    uint64_t carry = 0;
+    for (uint64_t start = 0; start < n; start += AGG_BLOCK * SEL_SCAN_ITEMS) {
+        const uint64_t i0 = start + (uint64_t)threadIdx.x * SEL_SCAN_ITEMS;
+        uint32_t c[SEL_SCAN_ITEMS];
+        uint32_t sum = 0;
+        #pragma unroll
+        for (uint32_t k = 0; k < SEL_SCAN_ITEMS; k++) {
+            c[k] = i0 + k < n ? counts[i0 + k] : 0u;
+            sum += c[k];
+        }
+        uint32_t inc = sum;
+        #pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const uint32_t t = __shfl_up(inc, d, WAVE);
+            if ((int)lane >= d) inc += t;
+        }
+        if (lane == WAVE - 1) wsum[wid] = inc;
+        __syncthreads();
+        uint32_t wbase = 0, blk = 0;
+        #pragma unroll
+        for (uint32_t w = 0; w < AGG_BLOCK / WAVE; w++) {
+            const uint32_t v = wsum[w];
+            if (w < wid) wbase += v;
+            blk += v;
+        }
+        uint64_t run = carry + wbase + (inc - sum);
+        #pragma unroll
+        for (uint32_t k = 0; k < SEL_SCAN_ITEMS; k++) {
+            if (i0 + k < n) bases[i0 + k] = run;
+            run += c[k];
+        }
+        carry += blk;
+        __syncthreads();    /* wsum is rewritten by the next pass */
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void select_emit_kernel(
+    const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
+    const uint32_t *__restrict__ rank, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, const uint64_t *__restrict__ mask,
+    const uint64_t *__restrict__ bases, const uint64_t *__restrict__ rowbase,
+    const SelectParams sp)
+{
+    __shared__ uint64_t s_word[SEL_SLICES];
+    __shared__ uint32_t s_pre[SEL_SLICES];   /* passing rows in earlier slices */
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    if (wid == 0) {         /* SEL_SLICES == WAVE: one lane per mask word */
+        const uint64_t w = mask[(uint64_t)blockIdx.x * SEL_SLICES + lane];
+        const uint32_t pc = (uint32_t)__popcll(w);
+        uint32_t inc = pc;
+        #pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const uint32_t t = __shfl_up(inc, d, WAVE);
+            if ((int)lane >= d) inc += t;
+        }
+        s_word[lane] = w;
+        s_pre[lane] = inc - pc;
+    }
+    __syncthreads();
+
+    const uint32_t gid = blockIdx.x / sp.tiles_per_group;
+    const uint32_t tile = blockIdx.x % sp.tiles_per_group;
+    const ColLoc *cols = colloc + groups[gid].colbase;
+    const uint64_t tile_base = bases[blockIdx.x];
+    const uint64_t first_row = rowbase[gid];
+
+    for (uint32_t sl = wid; sl < SEL_SLICES; sl += AGG_BLOCK / WAVE) {
+        const uint64_t word = s_word[sl];
+        if (word == 0) continue;                    /* wave-uniform skip */
+        const uint64_t bit = 1ull << lane;
+        if (!(word & bit)) continue;
+        const uint32_t row = tile * TILE_ROWS + sl * WAVE + lane;
+        const uint64_t idx = tile_base + s_pre[sl] +
+                             (uint32_t)__popcll(word & (bit - 1));
+        if (sp.row_numbers) sp.row_numbers[idx] = first_row + row;
+        for (uint32_t c = 0; c < sp.n_cols; c++) {
+            const SelCol &sc = sp.cols[c];
+            const ColLoc &cl = cols[sc.proj];
+            int64_t iv = 0; double fv = 0;
+            const bool ok = col_value(data, scratch, rank, cl, row, iv, fv);
+            if (!ok) { iv = 0; fv = 0; }            /* NULL slot: zero-filled */
+            /* raw ABI representation at the physical width; idx*width keeps
+             * every store naturally aligned */
+            switch (cl.type) {
+                case CSTRIPE_I8:  ((int8_t  *)sc.vals)[idx] = (int8_t)iv; break;
+                case CSTRIPE_I16: ((int16_t *)sc.vals)[idx] = (int16_t)iv; break;
+                case CSTRIPE_I32: ((int32_t *)sc.vals)[idx] = (int32_t)iv; break;
+                case CSTRIPE_I64: ((int64_t *)sc.vals)[idx] = iv; break;
+                case CSTRIPE_F32: ((float   *)sc.vals)[idx] = (float)fv; break;
+                case CSTRIPE_TEXT: ((uint32_t *)sc.vals)[idx] = (uint32_t)iv; break;
+                default:          ((double  *)sc.vals)[idx] = fv; break;
+            }
+            if (sc.nulls) sc.nulls[idx] = ok ? 0 : 1;
+        }
+    }
+}
+
+static int select_prepare(cstripe_scan *s, AggParams &p)
+{
+    cs_gpu_state *g = s->gpu;
+    cstripe_reader *r = s->r;
+    if (s->preds.size() > MAX_PREDS) { cs_set_err("too many preds"); return CSTRIPE_ERR_ARG; }
+    p.n_preds = (uint32_t)s->preds.size();
+    p.n_aggs = 0;
+    p.n_proj = g->n_proj;
+    p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
+    if (p.tiles_per_group == 0) p.tiles_per_group = 1;
+    p.n_groups = g->n_groups;
+    for (uint32_t i = 0; i < p.n_preds; i++) {
+        const cstripe_pred &q = s->preds[i];
+        p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
+        p.preds[i].op = (uint8_t)q.op;
+        uint8_t t = r->cols[q.column].type;
+        p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
+        p.preds[i].gend = (i + 1 == p.n_preds ||
+                           s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
+        p.preds[i].ival = q.ival;
+        p.preds[i].fval = q.fval;
+    }
+    for (hipEvent_t &e : g->sev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const uint64_t n_tiles = (uint64_t)g->n_groups * p.tiles_per_group;
+    if (n_tiles > 0 && !g->d_sel_mask) {
+        HIP_TRY(hipMalloc(&g->d_sel_mask, n_tiles * SEL_SLICES * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc(&g->d_sel_counts, n_tiles * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&g->d_sel_bases, n_tiles * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc(&g->d_sel_total, sizeof(uint64_t)));
+        /* table-wide row position of each surviving group's first row:
+         * cumulative rows over ALL chunk groups in directory order, pruned
+         * ones included — what cstripe_read_row counts on a predicate-free
+         * scan (ColumnarReadNextRow's rowNumber, columnar_reader.c:322-361) */
+        std::vector<uint64_t> h_rowbase(g->n_groups);
+        uint64_t row_base = 0;
+        size_t gi = 0;
+        for (uint32_t si = 0; si < r->stripes.size(); si++) {
+            const cs_stripe_info &st = r->stripes[si];
+            for (uint32_t k = 0; k < st.meta.chunk_count; k++) {
+                if (gi < s->sel.size() && s->sel[gi].stripe == si && s->sel[gi].chunk == k)
+                    h_rowbase[gi++] = row_base;
+                row_base += st.group_rows[k];
+            }
+        }
+        if (gi != s->sel.size()) { cs_set_err("scan_select: selection not in directory order"); return CSTRIPE_ERR; }
+        HIP_TRY(hipMalloc(&g->d_sel_rowbase, h_rowbase.size() * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(g->d_sel_rowbase, h_rowbase.data(),
+                               h_rowbase.size() * sizeof(uint64_t),
+                               hipMemcpyHostToDevice, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));   /* h_rowbase leaves scope */
+    }
+    return CSTRIPE_OK;
+}
+
+/* decode + mask + offsets on the scan's stream, then the one sync that
+ * brings the total back. sev[0..3] bracket decode / mask / offsets. */
+static int select_run_count(cstripe_scan *s, const AggParams &p)
+{
+    cs_gpu_state *g = s->gpu;
+    const uint32_t n_tiles = g->n_groups * p.tiles_per_group;
+    HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+    HIP_TRY(hipEventRecord(g->sev[0], g->stream));
+    { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+    HIP_TRY(hipEventRecord(g->sev[1], g->stream));
+    auto launchm = [&](auto *kern) {
+        hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_data, g->d_scratch, g->d_rank, g->d_groups,
+                           g->d_colloc, g->d_sel_mask, g->d_sel_counts, p);
+    };
+    if (p.n_preds == 5) launchm(select_mask_kernel<5>);
+    else if (p.n_preds == 1) launchm(select_mask_kernel<1>);
+    else if (p.n_preds == 2) launchm(select_mask_kernel<2>);
+    else launchm(select_mask_kernel<-1>);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->sev[2], g->stream));
+    hipLaunchKernelGGL(select_offsets_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_sel_counts, g->d_sel_bases, g->d_sel_total, n_tiles);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->sev[3], g->stream));
+    uint64_t h_total = 0;
+    int h_err = 0;
+    HIP_TRY(hipMemcpyAsync(&h_total, g->d_sel_total, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    float ms_d = 0, ms_m = 0, ms_o = 0;
+    (void)hipEventElapsedTime(&ms_d, g->sev[0], g->sev[1]);
+    (void)hipEventElapsedTime(&ms_m, g->sev[1], g->sev[2]);
+    (void)hipEventElapsedTime(&ms_o, g->sev[2], g->sev[3]);
+    s->last_decode_ms = ms_d;
+    s->last_select_mask_ms = ms_m;
+    s->last_select_offsets_ms = ms_o;
+    s->last_select_emit_ms = 0;
+    s->last_agg_ms = 0;
+    s->last_kernel_ms = ms_d + ms_m + ms_o;
+    g->sel_total = h_total;
+    g->sel_cached = true;
+    return CSTRIPE_OK;
+}
+
+static void select_zero_timing(cstripe_scan *s)
+{
+    s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
+    s->last_select_mask_ms = s->last_select_offsets_ms = s->last_select_emit_ms = 0;
+}
+
+int csgpu_select_count(cstripe_scan *s, uint64_t *n_rows)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    cs_gpu_state *g = s->gpu;
+    AggParams p{};
+    { int _rc = select_prepare(s, p); if (_rc != CSTRIPE_OK) return _rc; }
+    if (g->n_groups == 0) {
+        select_zero_timing(s);
+        *n_rows = 0;
+        return CSTRIPE_OK;
+    }
+    { int _rc = select_run_count(s, p); if (_rc != CSTRIPE_OK) return _rc; }
+    *n_rows = g->sel_total;
+    return CSTRIPE_OK;
+}
+
+int csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
+                 int dst_on_device)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    cs_gpu_state *g = s->gpu;
+    cstripe_reader *r = s->r;
+    const uint32_t n_cols = r->head.column_count;
+
+    SelectParams sp{};
+    uint8_t widths[MAX_PROJ] = {0};
+    uint32_t dst_col[MAX_PROJ] = {0};
+    for (uint32_t c = 0; c < n_cols && out->col_values; c++) {
+        if (!out->col_values[c]) continue;
+        const int pj = g->proj_of_col[c];
+        if (pj < 0) { cs_set_err("scan_select: column %u not projected", c); return CSTRIPE_ERR_ARG; }
+        widths[sp.n_cols] = (uint8_t)csf_type_width(r->cols[c].type);
+        dst_col[sp.n_cols] = c;
+        sp.cols[sp.n_cols].proj = (uint32_t)pj;
+        sp.n_cols++;
+    }
+
+    AggParams p{};
+    { int _rc = select_prepare(s, p); if (_rc != CSTRIPE_OK) return _rc; }
+    sp.tiles_per_group = p.tiles_per_group;
+    if (g->n_groups == 0) {
+        select_zero_timing(s);
+        out->n_rows = 0;
+        return CSTRIPE_OK;
+    }
+
+    float ms_d = 0, ms_m = 0, ms_o = 0;
+    if (!g->sel_cached) {
+        { int _rc = select_run_count(s, p); if (_rc != CSTRIPE_OK) return _rc; }
+        ms_d = (float)s->last_decode_ms;
+        ms_m = (float)s->last_select_mask_ms;
+        ms_o = (float)s->last_select_offsets_ms;
+    }
+    const uint64_t n = g->sel_total;
+    if (capacity < n) {
+        cs_set_err("scan_select: capacity %llu < %llu selected rows",
+                   (unsigned long long)capacity, (unsigned long long)n);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (n == 0) {
+        s->last_decode_ms = ms_d;
+        s->last_select_mask_ms = ms_m;
+        s->last_select_offsets_ms = ms_o;
+        s->last_select_emit_ms = 0;
+        s->last_agg_ms = 0;
+        s->last_kernel_ms = ms_d + ms_m + ms_o;
+        out->n_rows = 0;
+        return CSTRIPE_OK;
+    }
+
+    /* destinations: the caller's device pointers, or slices of the owned
+     * compaction buffer (sized by the count) copied back per stream */
+    uint64_t off_vals[MAX_PROJ], off_nulls[MAX_PROJ], off_rn = 0;
+    if (dst_on_device) {
+        for (uint32_t i = 0; i < sp.n_cols; i++) {
+            sp.cols[i].vals = (uint8_t *)out->col_values[dst_col[i]];
+            sp.cols[i].nulls = out->col_nulls ? out->col_nulls[dst_col[i]] : nullptr;
+        }
+        sp.row_numbers = out->row_numbers;
+    } else {
+        uint64_t need = 0;
+        for (uint32_t i = 0; i < sp.n_cols; i++) {
+            off_vals[i] = need;
+            need = align_up(need + n * widths[i], 16);
+            off_nulls[i] = need;
+            if (out->col_nulls && out->col_nulls[dst_col[i]])
+                need = align_up(need + n, 16);
+        }
+        off_rn = need;
+        if (out->row_numbers) need += n * sizeof(uint64_t);
+        if (need > g->sel_out_bytes) {
+            if (g->d_sel_out) HIP_TRY(hipFree(g->d_sel_out));
+            g->d_sel_out = nullptr;
+            g->sel_out_bytes = 0;
+            HIP_TRY(hipMalloc(&g->d_sel_out, need));
+            g->sel_out_bytes = need;
+        }
+        for (uint32_t i = 0; i < sp.n_cols; i++) {
+            sp.cols[i].vals = g->d_sel_out + off_vals[i];
+            sp.cols[i].nulls = (out->col_nulls && out->col_nulls[dst_col[i]])
+                                   ? g->d_sel_out + off_nulls[i] : nullptr;
+        }
+        sp.row_numbers = out->row_numbers ? (uint64_t *)(g->d_sel_out + off_rn) : nullptr;
+    }
+
+    const uint32_t n_tiles = g->n_groups * p.tiles_per_group;
+    HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+    HIP_TRY(hipEventRecord(g->sev[0], g->stream));
+    /* the emit pass gathers from decoded streams; decode re-runs per call
+     * like scan_agg, so the timing means the same thing */
+    { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+    HIP_TRY(hipEventRecord(g->sev[1], g->stream));
+    hipLaunchKernelGGL(select_emit_kernel, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_data, g->d_scratch, g->d_rank, g->d_groups, g->d_colloc,
+                       g->d_sel_mask, g->d_sel_bases, g->d_sel_rowbase, sp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->sev[2], g->stream));
+    int h_err = 0;
+    HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    if (!dst_on_device) {
+        for (uint32_t i = 0; i < sp.n_cols; i++) {
+            HIP_TRY(hipMemcpyAsync(out->col_values[dst_col[i]], sp.cols[i].vals,
+                                   n * widths[i], hipMemcpyDeviceToHost, g->stream));
+            if (sp.cols[i].nulls)
+                HIP_TRY(hipMemcpyAsync(out->col_nulls[dst_col[i]], sp.cols[i].nulls,
+                                       n, hipMemcpyDeviceToHost, g->stream));
+        }
+        if (sp.row_numbers)
+            HIP_TRY(hipMemcpyAsync(out->row_numbers, sp.row_numbers,
+                                   n * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+    }
+    float ms_d2 = 0, ms_e = 0;
+    (void)hipEventElapsedTime(&ms_d2, g->sev[0], g->sev[1]);
+    (void)hipEventElapsedTime(&ms_e, g->sev[1], g->sev[2]);
+    s->last_decode_ms = ms_d + ms_d2;
+    s->last_select_mask_ms = ms_m;
+    s->last_select_offsets_ms = ms_o;
+    s->last_select_emit_ms = ms_e;
+    s->last_agg_ms = 0;
+    s->last_kernel_ms = ms_d + ms_d2 + ms_m + ms_o + ms_e;
+    out->n_rows = n;
+    return CSTRIPE_OK;
 }
 
 /* =====================================================================

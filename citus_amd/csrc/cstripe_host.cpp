@@ -1353,6 +1353,29 @@ extern "C" int cstripe_scan_next_batch(cstripe_scan *s, cstripe_batch *batch)
     return csgpu_next_batch(s, batch);
 }
 
+extern "C" int cstripe_scan_select_count(cstripe_scan *s, uint64_t *n_rows)
+{
+    if (!s || !n_rows) { cs_set_err("scan_select_count: bad args"); return CSTRIPE_ERR_ARG; }
+    return csgpu_select_count(s, n_rows);
+}
+
+extern "C" int cstripe_scan_select(cstripe_scan *s, cstripe_rows *out,
+                                   uint64_t capacity, int dst_on_device)
+{
+    if (!s || !out) { cs_set_err("scan_select: bad args"); return CSTRIPE_ERR_ARG; }
+    return csgpu_select(s, out, capacity, dst_on_device);
+}
+
+extern "C" int cstripe_scan_last_select_ms(const cstripe_scan *s, double *mask_ms,
+                                           double *offsets_ms, double *emit_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (mask_ms) *mask_ms = s->last_select_mask_ms;
+    if (offsets_ms) *offsets_ms = s->last_select_offsets_ms;
+    if (emit_ms) *emit_ms = s->last_select_emit_ms;
+    return CSTRIPE_OK;
+}
+
 /* ============================ combine ============================ */
 
 static bool agg_is_count(uint32_t k)

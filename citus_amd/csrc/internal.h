@@ -68,6 +68,9 @@ struct cstripe_scan {
     double last_kernel_ms = 0.0;
     double last_decode_ms = 0.0;
     double last_agg_ms = 0.0;
+    double last_select_mask_ms = 0.0;     /* scan_select per-kernel split */
+    double last_select_offsets_ms = 0.0;
+    double last_select_emit_ms = 0.0;
     /* random-access read cache (the reference keeps the current stripe
      * open across ColumnarReadRowByRowNumber calls the same way) */
     int64_t rr_gi = -1;
@@ -93,6 +96,11 @@ int  csgpu_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
                cstripe_group_result *gr, cstripe_partial *out);
 int  csgpu_next_batch(cstripe_scan *s, cstripe_batch *batch);
 int  csgpu_fetch_batch(cstripe_scan *s, uint32_t gi, cstripe_batch *batch);
+/* filtered row materialisation (mask -> offsets -> emit kernels); the mask
+ * and bases stay cached on the scan until scan_end / restage */
+int  csgpu_select_count(cstripe_scan *s, uint64_t *n_rows);
+int  csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
+                  int dst_on_device);
 
 /* device write path: one chunk's columns compressed on the GPU (canonical
  * parses where the data fits, raw copy-back otherwise) */

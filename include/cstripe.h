@@ -334,6 +334,68 @@ int cstripe_read_row(cstripe_scan *s, uint64_t row_number,
 int cstripe_scan_next_batch(cstripe_scan *s, cstripe_batch *batch);
 int cstripe_scan_rewind(cstripe_scan *s);
 
+/* ---- filtered row materialisation (device-side SELECT ... WHERE) ----
+ * The qual loop of ColumnarScanNext (columnar_customscan.c:1854-1913: read a
+ * row, run ExecQual, return the rows that pass) with the ROWS coming out, in
+ * column-major form, instead of an aggregate over them. Caller provides the
+ * destinations; capacity is in rows. */
+typedef struct cstripe_rows {
+    uint64_t   n_rows;       /* out: rows that passed, in scan order */
+    void     **col_values;   /* in: [n_cols] destinations, each >= capacity*width;
+                              * NULL = column not wanted */
+    uint8_t  **col_nulls;    /* in: [n_cols] or NULL; 1 = null, like cstripe_batch */
+    uint64_t  *row_numbers;  /* in: capacity entries, or NULL */
+} cstripe_rows;
+
+/* cstripe_scan_select_count: number of rows cstripe_scan_select returns.
+ * Runs the predicate pass on device (one pass bit per row + a prefix scan
+ * of per-tile counts) and keeps both on the scan; a following
+ * cstripe_scan_select reuses them. Predicates are fixed at scan_begin, so
+ * only cstripe_scan_end / a restage drops that cache.
+ *
+ * cstripe_scan_select:
+ *  - Filter: a row passes iff the scan's CNF predicate set is true,
+ *    evaluated exactly as cstripe_scan_agg evaluates it — OR groups, a NULL
+ *    operand fails its atom, PG float ordering (NaN greatest, equal to
+ *    itself), TEXT compares whole slots; zero predicates select every row.
+ *    Chunk groups removed by min/max pruning contribute nothing.
+ *  - Order: scan order (ascending row number), deterministic, identical on
+ *    every call.
+ *  - Values: written at the column's physical width in the ABI's raw
+ *    representation (TEXT = the 4-byte slot); NULL slots are zero-filled
+ *    with col_nulls[c][i] = 1. A wanted column must be projected (in
+ *    cols_mask or a predicate column), else CSTRIPE_ERR_ARG.
+ *  - Row numbers: the reference's rowNumber out-parameter
+ *    (ColumnarReadNextRow, columnar_reader.c:322-361) — the 0-based
+ *    table-wide row position cstripe_read_row accepts on a predicate-free
+ *    scan of the same reader: cumulative rows over ALL chunk groups in
+ *    directory order, so a surviving chunk's base counts the pruned chunks
+ *    before it, and positions continue across shard files.
+ *  - Capacity: capacity < n_rows returns CSTRIPE_ERR_ARG (the message names
+ *    both numbers) and writes nothing.
+ *  - Destinations: dst_on_device != 0 — every destination pointer is device
+ *    memory on the scan's device and results never touch the host (they can
+ *    feed cstripe_write_rows_device directly). Otherwise destinations are
+ *    host memory: the library compacts into a device buffer it owns, sized
+ *    by the count, and issues one DtoH copy per wanted stream.
+ *  - Errors: both need a staged scan (CSTRIPE_ERR_NOGPU otherwise); a device
+ *    decode error flag surfaces as CSTRIPE_ERR_FORMAT.
+ *  - Both are re-invocable and may be interleaved with scan_agg,
+ *    scan_agg_grouped, next_batch and read_row on the same scan without
+ *    changing any of their results. Decode kernels re-run per call, like
+ *    cstripe_scan_agg. cstripe_scan_last_kernel_ms /
+ *    cstripe_scan_last_decode_kernel_ms then report the last select (or
+ *    select_count) call.
+ *  - Zero selected chunk groups or zero passing rows: CSTRIPE_OK, n_rows = 0. */
+int cstripe_scan_select_count(cstripe_scan *s, uint64_t *n_rows);
+int cstripe_scan_select(cstripe_scan *s, cstripe_rows *out,
+                        uint64_t capacity, int dst_on_device);
+/* per-kernel device time of the last select / select_count call,
+ * milliseconds; a pass that was served from the scan's cache reads 0.
+ * Any out pointer may be NULL. */
+int cstripe_scan_last_select_ms(const cstripe_scan *s, double *mask_ms,
+                                double *offsets_ms, double *emit_ms);
+
 /* 1 when the last cstripe_scan_agg ran the fused decode+filter+aggregate
  * kernel (no scratch round trip), 0 for the two-kernel path */
 int cstripe_scan_last_fused(const cstripe_scan *s);
