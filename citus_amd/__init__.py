@@ -102,6 +102,29 @@ class Rows(C.Structure):
                 ("row_numbers", C.c_void_p)]
 
 
+MAX_HASH_KEY_COLS = 4
+MAX_HASH_GROUPS = 1 << 24
+
+
+class HGroups(C.Structure):
+    _fields_ = [("n_groups", C.c_uint64),
+                ("keys", C.c_void_p * MAX_HASH_KEY_COLS),
+                ("key_nulls", C.c_void_p * MAX_HASH_KEY_COLS),
+                ("partials", C.c_void_p)]
+
+
+def partial_dtype():
+    """numpy structured dtype mirroring cstripe_partial (40 bytes)"""
+    import numpy as np
+    return np.dtype([("i128_lo", "<i8"), ("i128_hi", "<i8"), ("f64", "<f8"),
+                     ("count", "<i8"), ("is_null", "u1"), ("_pad", "u1", (7,))])
+
+
+def partial_i128(p):
+    """signed 128-bit Python int of one structured-array partial"""
+    return (int(p["i128_hi"]) << 64) | (int(p["i128_lo"]) & ((1 << 64) - 1))
+
+
 class GroupResult(C.Structure):
     _fields_ = [("n_groups", C.c_uint32), ("keys", C.c_uint32 * 64)]
 
@@ -170,6 +193,17 @@ _select = _sig("cstripe_scan_select", C.c_int,
 _last_select_ms = _sig("cstripe_scan_last_select_ms", C.c_int,
                        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(C.c_double)])
+_scan_agg_hashed = _sig("cstripe_scan_agg_hashed", C.c_int,
+                        [C.c_void_p, C.POINTER(AggSpec), C.c_uint32,
+                         C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64,
+                         C.POINTER(HGroups)])
+_last_hash_ms = _sig("cstripe_scan_last_hash_ms", C.c_int,
+                     [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                      C.POINTER(C.c_double)])
+_combine_groups = _sig("cagg_combine_groups", C.c_int,
+                       [C.POINTER(AggSpec), C.c_uint32, C.c_uint32,
+                        C.POINTER(HGroups), C.c_uint32, C.POINTER(HGroups),
+                        C.c_uint64])
 _rewind = _sig("cstripe_scan_rewind", C.c_int, [C.c_void_p])
 _last_fused = _sig("cstripe_scan_last_fused", C.c_int, [C.c_void_p])
 _last_kernel_ms = _sig("cstripe_scan_last_kernel_ms", C.c_double, [C.c_void_p])
@@ -437,6 +471,64 @@ def make_aggs(aggs):
     return arr
 
 
+def _alloc_hgroups(n_key_cols, n_aggs, capacity):
+    """numpy destinations for `capacity` groups + the cstripe_hgroups
+    pointing at them (the arrays must outlive the call)"""
+    import numpy as np
+    nk = min(n_key_cols, MAX_HASH_KEY_COLS)
+    bufs = {"keys": [np.zeros(capacity, dtype=np.int64) for _ in range(nk)],
+            "key_nulls": [np.zeros(capacity, dtype=np.uint8) for _ in range(nk)],
+            "partials": np.zeros((capacity, n_aggs), dtype=partial_dtype())}
+    hg = HGroups()
+    for k in range(nk):
+        hg.keys[k] = bufs["keys"][k].ctypes.data
+        hg.key_nulls[k] = bufs["key_nulls"][k].ctypes.data
+    hg.partials = bufs["partials"].ctypes.data
+    return bufs, hg
+
+
+def _hgroups_result(bufs, n):
+    # copies, so a large capacity's buffers are not kept alive by the result
+    return {"n_groups": n,
+            "keys": [a[:n].copy() for a in bufs["keys"]],
+            "key_nulls": [a[:n].copy() for a in bufs["key_nulls"]],
+            "partials": bufs["partials"][:n].copy()}
+
+
+def combine_groups(aggs, n_key_cols, results, capacity=None):
+    """The coordinator merge per group (cagg_combine_groups): results is a
+    list of agg_hashed()-shaped dicts (per shard/GPU, any order, duplicate
+    keys allowed); returns one dict of the same shape, sorted. capacity
+    defaults to the sum of the inputs' group counts, which always fits."""
+    import numpy as np
+    n_aggs = len(aggs)
+    arr = make_aggs(aggs)
+    parts = (HGroups * max(1, len(results)))()
+    keep = []
+    for i, res in enumerate(results):
+        n = int(res["n_groups"])
+        parts[i].n_groups = n
+        pa = np.ascontiguousarray(res["partials"], dtype=partial_dtype())
+        if pa.size != n * n_aggs:
+            raise CStripeError("combine_groups: partials shape does not match "
+                               f"n_groups={n}, n_aggs={n_aggs}")
+        keep.append(pa)
+        parts[i].partials = pa.ctypes.data
+        for k in range(min(n_key_cols, MAX_HASH_KEY_COLS, len(res["keys"]))):
+            ka = np.ascontiguousarray(res["keys"][k], dtype=np.int64)
+            na = np.ascontiguousarray(res["key_nulls"][k], dtype=np.uint8)
+            keep += [ka, na]
+            parts[i].keys[k] = ka.ctypes.data
+            parts[i].key_nulls[k] = na.ctypes.data
+    cap = max(1, sum(int(r["n_groups"]) for r in results))
+    if capacity is not None:
+        cap = int(capacity)
+    bufs, hg = _alloc_hgroups(n_key_cols, n_aggs, max(cap, 1))
+    _check(_combine_groups(arr, n_aggs, n_key_cols, parts, len(results),
+                           C.byref(hg), cap), "combine_groups")
+    return _hgroups_result(bufs, hg.n_groups)
+
+
 class Scan:
     def __init__(self, reader, cols_mask, preds):
         self._preds = make_preds(preds)
@@ -511,6 +603,28 @@ class Scan:
             key = decode_group_key(gr.keys[g])
             res[key] = [out[g * len(aggs) + a] for a in range(len(aggs))]
         return res
+
+    def agg_hashed(self, aggs, key_cols, capacity):
+        """Hashed GROUP BY (cstripe_scan_agg_hashed) over 1..4 integer/TEXT
+        key columns, at most `capacity` groups. Returns {"n_groups",
+        "keys": [int64 array per key col], "key_nulls": [uint8 arrays],
+        "partials": structured array (n_groups, n_aggs) of partial_dtype()},
+        sorted ascending by key tuple, NULL keys last."""
+        arr = make_aggs(aggs)
+        kc = (C.c_uint32 * max(1, len(key_cols)))(*key_cols)
+        bufs, hg = _alloc_hgroups(len(key_cols), len(aggs),
+                                  min(max(int(capacity), 1), MAX_HASH_GROUPS))
+        _check(_scan_agg_hashed(self._h, arr, len(aggs), kc, len(key_cols),
+                                capacity, C.byref(hg)), "scan_agg_hashed")
+        return _hgroups_result(bufs, hg.n_groups)
+
+    @property
+    def last_hash_ms(self):
+        """(init, scan, compact) device ms of the last agg_hashed call"""
+        i, s, c = C.c_double(), C.c_double(), C.c_double()
+        _check(_last_hash_ms(self._h, C.byref(i), C.byref(s), C.byref(c)),
+               "scan_last_hash_ms")
+        return i.value, s.value, c.value
 
     def next_batch(self, col_arrays, null_arrays=None):
         """col_arrays: dict col_index -> numpy array (capacity chunk rows).

@@ -149,6 +149,16 @@ struct cs_gpu_state {
     bool sel_cached = false;
     uint64_t sel_total = 0;
     hipEvent_t sev[4] = {nullptr, nullptr, nullptr, nullptr};
+    /* scan_agg_hashed: open-addressing table (key words + accumulator
+     * cells), the dense compaction target and its counter; grown when
+     * capacity or n_aggs needs it */
+    unsigned long long *d_hkeys = nullptr;     /* [slots] packed keys / EMPTY */
+    struct ThreadAcc *d_hcells = nullptr;      /* [slots * n_aggs] */
+    unsigned long long *d_hokeys = nullptr;    /* [capacity] compacted keys */
+    AccCell *d_hocells = nullptr;              /* [capacity * n_aggs] */
+    unsigned long long *d_hcount = nullptr;    /* one word: occupied slots */
+    uint64_t hkeys_slots = 0, hcells_n = 0, hokeys_n = 0, hocells_n = 0;
+    hipEvent_t hev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 
     uint64_t data_bytes = 0;
     uint64_t scratch_bytes = 0;
@@ -3047,6 +3057,12 @@ void csgpu_release(cstripe_scan *s)
     if (g->d_sel_total) HIP_DROP(hipFree(g->d_sel_total));
     if (g->d_sel_rowbase) HIP_DROP(hipFree(g->d_sel_rowbase));
     if (g->d_sel_out) HIP_DROP(hipFree(g->d_sel_out));
+    if (g->d_hkeys) HIP_DROP(hipFree(g->d_hkeys));
+    if (g->d_hcells) HIP_DROP(hipFree(g->d_hcells));
+    if (g->d_hokeys) HIP_DROP(hipFree(g->d_hokeys));
+    if (g->d_hocells) HIP_DROP(hipFree(g->d_hocells));
+    if (g->d_hcount) HIP_DROP(hipFree(g->d_hcount));
+    for (hipEvent_t e : g->hev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->sev) if (e) HIP_DROP(hipEventDestroy(e));
     if (g->ev0) HIP_DROP(hipEventDestroy(g->ev0));
     if (g->ev1) HIP_DROP(hipEventDestroy(g->ev1));
@@ -4848,6 +4864,619 @@ int csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
     s->last_agg_ms = 0;
     s->last_kernel_ms = ms_d + ms_d2 + ms_m + ms_o + ms_e;
     out->n_rows = n;
+    return CSTRIPE_OK;
+}
+
+/* =====================================================================
+ * Hashed GROUP BY (cstripe_scan_agg_hashed): the worker HashAggregate of
+ * the reference's grouped plan (multi_explain.out:80-82,
+ * multi_logical_optimizer.c:1807-1885) with no bound on the group count
+ * but the caller's capacity. Three kernels on the scan's stream:
+ *
+ *   hash_init_kernel     key words = EMPTY, cells = acc_init identities.
+ *                        Every call: a repeated call must not add onto the
+ *                        previous call's sums.
+ *   hash_agg_kernel      grid-stride blocks over (chunk group x 4096-row
+ *                        tile), predicates exactly as grouped_agg_kernel.
+ *                        The key tuple packs into ONE 64-bit word (host
+ *                        picks per-column [lo, hi] from the selected
+ *                        chunks' skip nodes), so claiming a slot is a single
+ *                        8-byte CAS. Rows fold into a per-block LDS table
+ *                        first (bounded probes; a row that finds no LDS
+ *                        slot goes straight to the global table) — without
+ *                        it a low-cardinality query funnels every row into
+ *                        a few global words, and device atomics on one word
+ *                        serialise. After its last tile the block flushes
+ *                        its occupied LDS slots into the global table.
+ *   hash_compact_kernel  appends the occupied global slots to dense arrays
+ *                        through one device counter (wave-aggregated add);
+ *                        the host sorts, so append order is free.
+ *
+ * No flag, fence, publish or spin-wait exists: every global word another
+ * block may touch during hash_agg_kernel is updated only by device-scope
+ * atomic read-modify-writes (CAS / add / min / max), and everything else is
+ * visible at the kernel boundaries on the stream. The only plain loads of
+ * such words are the first guess of the f64 min/max CAS loops: a stale
+ * guess is an OLDER value of a monotonic word, so "my value does not
+ * improve on it" still holds for the current value, and any other outcome
+ * is re-checked by the CAS itself.
+ * Every probe loop is bounded (LDS: HASH_LDS_PROBES; global: `slots`).
+ * ===================================================================== */
+
+#define HASH_EMPTY      (~0ull)
+#define HASH_NONE       (~0ull)
+#define HASH_LDS_PROBES 8
+#define HASH_LDS_BUDGET (64u * 1024u)   /* bytes/block: two blocks fit a CU */
+#define HASH_GRID       1024
+#define HASH_ERR_RANGE  32              /* key outside its skip-node range */
+#define HASH_ERR_FULL   64              /* global table full */
+#define HASH_ERR_TEXT   128             /* order-key packed TEXT slot not canonical */
+
+struct HashParams {
+    AggParams base;
+    uint32_t n_key_cols;
+    uint32_t n_work;                    /* n_groups * tiles_per_group */
+    uint32_t lds_slots;                 /* 0 = no LDS table, else power of 2 */
+    uint32_t pad;
+    uint32_t kproj[CSTRIPE_MAX_HASH_KEY_COLS];
+    uint32_t kshift[CSTRIPE_MAX_HASH_KEY_COLS];
+    int64_t  klo[CSTRIPE_MAX_HASH_KEY_COLS];
+    uint64_t kspan[CSTRIPE_MAX_HASH_KEY_COLS];   /* hi - lo, unsigned */
+    uint32_t klex[CSTRIPE_MAX_HASH_KEY_COLS];    /* TEXT packed by order key */
+    uint64_t slots;                     /* global table, power of 2 */
+};
+
+/* a TEXT slot's C-collation order key (csf_text_lex_key, format.h) and its
+ * inverse: the key is injective over canonical short-varlena slots (header
+ * = payload length, zero padding, no NUL in the payload), which is what
+ * lets a TEXT key column pack into its skip nodes' [min, max] */
+__host__ __device__ inline uint32_t hash_text_lex(uint32_t slot)
+{
+    return (((slot >> 8) & 0xFFu) << 16) | (((slot >> 16) & 0xFFu) << 8) |
+           ((slot >> 24) & 0xFFu);
+}
+
+__host__ __device__ inline uint32_t hash_text_slot(uint32_t lex)
+{
+    const uint32_t b1 = (lex >> 16) & 0xFFu, b2 = (lex >> 8) & 0xFFu, b3 = lex & 0xFFu;
+    const uint32_t len = b3 ? 3u : (b2 ? 2u : (b1 ? 1u : 0u));
+    return (((len + 1u) << 1) | 1u) | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+
+__device__ inline uint64_t hash_mix64(uint64_t x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+/* claim-or-find the key's slot in the global table: linear probing, one
+ * 8-byte CAS per probe, at most `slots` probes; a full table sets
+ * HASH_ERR_FULL and the caller drops the contribution (the host then fails
+ * the whole call) */
+__device__ inline uint64_t hash_global_insert(unsigned long long *gkeys, uint64_t slots,
+                                              uint64_t h, uint64_t key, int *err)
+{
+    const uint64_t mask = slots - 1;
+    uint64_t slot = h & mask;
+    for (uint64_t n = 0; n < slots; n++) {
+        const unsigned long long prev = atomicCAS(&gkeys[slot], HASH_EMPTY, key);
+        if (prev == HASH_EMPTY || prev == key) return slot;
+        slot = (slot + 1) & mask;
+    }
+    atomicOr(err, HASH_ERR_FULL);
+    return HASH_NONE;
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void hash_init_kernel(
+    unsigned long long *__restrict__ gkeys, ThreadAcc *__restrict__ gcells,
+    unsigned long long *__restrict__ count, const HashParams hp)
+{
+    const uint32_t n_aggs = hp.base.n_aggs;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < hp.slots;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        gkeys[i] = HASH_EMPTY;
+        for (uint32_t a = 0; a < n_aggs; a++) {
+            ThreadAcc z;
+            acc_init(z, hp.base.aggs[a].kind);
+            gcells[i * n_aggs + a] = z;
+        }
+    }
+}
+
+template <int NAGGS>
+__global__ __launch_bounds__(AGG_BLOCK) void hash_agg_kernel(
+    const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
+    const uint32_t *__restrict__ rank, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, unsigned long long *gkeys,
+    ThreadAcc *gcells, int *err, const HashParams hp)
+{
+    const AggParams &params = hp.base;
+    const uint32_t n_aggs_ct = NAGGS >= 0 ? (uint32_t)NAGGS : params.n_aggs;
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint32_t n_waves = AGG_BLOCK / WAVE;
+    const uint32_t L = hp.lds_slots;
+
+    extern __shared__ __attribute__((aligned(16))) uint8_t hsh[];
+    unsigned long long *lkeys = (unsigned long long *)hsh;          /* [L] */
+    ThreadAcc *lcells = (ThreadAcc *)(hsh + (size_t)L * sizeof(unsigned long long));
+
+    for (uint32_t i = threadIdx.x; i < L; i += AGG_BLOCK) {
+        lkeys[i] = HASH_EMPTY;
+        for (uint32_t a = 0; a < n_aggs_ct; a++)
+            acc_init(lcells[i * n_aggs_ct + a], params.aggs[a].kind);
+    }
+    __syncthreads();
+
+    for (uint32_t work = blockIdx.x; work < hp.n_work; work += gridDim.x) {
+        const uint32_t gid = work / params.tiles_per_group;
+        const uint32_t tile = work % params.tiles_per_group;
+        const GroupDesc g = groups[gid];
+        const ColLoc *cols = colloc + g.colbase;
+        uint32_t row_start = tile * TILE_ROWS;
+        uint32_t row_end = min(row_start + TILE_ROWS, g.row_count);
+
+        for (uint32_t base_row = row_start + wid * WAVE; base_row < row_end;
+             base_row += WAVE * n_waves) {
+            uint32_t row = base_row + lane;
+            bool pass = row < row_end;
+            if (pass) {
+                int last_proj = -1;
+                int64_t liv = 0; double lfv = 0; bool lok = false;
+                bool gv = false;
+                for (uint32_t p = 0; p < params.n_preds; p++) {
+                    const PredD &pr = params.preds[p];
+                    if ((int)pr.proj != last_proj) {
+                        lok = col_value(data, scratch, rank, cols[pr.proj], row, liv, lfv);
+                        last_proj = (int)pr.proj;
+                    }
+                    gv = gv | (lok && pred_eval(pr, liv, lfv));
+                    if (pr.gend) { pass = pass & gv; gv = false; }
+                }
+            }
+            if (!pass) continue;
+            /* packed key: per column 0 = NULL, else 1 + (v - lo); NULL keys
+             * form their own group (HashAggregate treats NULLs as equal) */
+            uint64_t key = 0;
+            bool in_range = true, bad_text = false;
+            for (uint32_t kc = 0; kc < hp.n_key_cols; kc++) {
+                int64_t kv; double kf;
+                uint64_t code = 0;
+                if (col_value(data, scratch, rank, cols[hp.kproj[kc]], row, kv, kf)) {
+                    if (hp.klex[kc]) {
+                        const uint32_t lex = hash_text_lex((uint32_t)kv);
+                        if (hash_text_slot(lex) != (uint32_t)kv) bad_text = true;
+                        kv = (int64_t)lex;
+                    }
+                    const uint64_t d = (uint64_t)kv - (uint64_t)hp.klo[kc];
+                    in_range = in_range && d <= hp.kspan[kc];
+                    code = d + 1;
+                }
+                key |= code << hp.kshift[kc];
+            }
+            if (bad_text) {
+                atomicOr(err, HASH_ERR_TEXT);
+                continue;
+            }
+            if (!in_range) {        /* skip nodes lie: fail, never mis-group */
+                atomicOr(err, HASH_ERR_RANGE);
+                continue;
+            }
+            const uint64_t h = hash_mix64(key);
+            uint32_t lslot = (uint32_t)(h >> 32) & (L - 1);
+            bool in_lds = false;
+            if (L) {
+                for (uint32_t pr = 0; pr < HASH_LDS_PROBES; pr++) {
+                    const unsigned long long prev = atomicCAS(&lkeys[lslot], HASH_EMPTY, key);
+                    if (prev == HASH_EMPTY || prev == key) { in_lds = true; break; }
+                    lslot = (lslot + 1) & (L - 1);
+                }
+            }
+            if (in_lds) {
+                ThreadAcc *cell = lcells + (size_t)lslot * n_aggs_ct;
+                for (uint32_t a = 0; a < n_aggs_ct; a++) {
+                    PrepAcc p;
+                    acc_prepare(p, params.aggs[a], data, scratch, rank, cols, row);
+                    acc_apply_atomic(&cell[a], params.aggs[a].kind, p);
+                }
+            } else {
+                const uint64_t gs = hash_global_insert(gkeys, hp.slots, h, key, err);
+                if (gs == HASH_NONE) continue;
+                ThreadAcc *cell = gcells + gs * n_aggs_ct;
+                for (uint32_t a = 0; a < n_aggs_ct; a++) {
+                    PrepAcc p;
+                    acc_prepare(p, params.aggs[a], data, scratch, rank, cols, row);
+                    acc_apply_atomic(&cell[a], params.aggs[a].kind, p);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    /* flush: every thread merges the occupied LDS slots it owns into the
+     * global table — same insert, then the carry-exact atomic merge */
+    for (uint32_t i = threadIdx.x; i < L; i += AGG_BLOCK) {
+        const unsigned long long key = lkeys[i];
+        if (key == HASH_EMPTY) continue;
+        const uint64_t gs = hash_global_insert(gkeys, hp.slots, hash_mix64(key), key, err);
+        if (gs == HASH_NONE) continue;
+        ThreadAcc *cell = gcells + gs * n_aggs_ct;
+        for (uint32_t a = 0; a < n_aggs_ct; a++) {
+            const ThreadAcc &t = lcells[i * n_aggs_ct + a];
+            const AccCell c{t.lo, t.hi, t.f, t.cnt};
+            cell_merge_atomic(&cell[a], params.aggs[a].kind, c);
+        }
+    }
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void hash_compact_kernel(
+    const unsigned long long *__restrict__ gkeys, const ThreadAcc *__restrict__ gcells,
+    unsigned long long *__restrict__ count, unsigned long long *__restrict__ okeys,
+    AccCell *__restrict__ ocells, uint64_t capacity, const HashParams hp)
+{
+    const uint32_t n_aggs = hp.base.n_aggs;
+    const uint32_t lane = threadIdx.x % WAVE;
+    /* wave-uniform trip count: the ballot below needs every lane present */
+    for (uint64_t base = (uint64_t)blockIdx.x * AGG_BLOCK; base < hp.slots;
+         base += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        unsigned long long key = HASH_EMPTY;
+        if (i < hp.slots) key = gkeys[i];
+        const bool occ = key != HASH_EMPTY;
+        const uint64_t m = __ballot(occ);
+        if (m == 0) continue;
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        unsigned long long wbase = 0;
+        if ((int)lane == leader)
+            wbase = atomicAdd(count, (unsigned long long)__popcll(m));
+        wbase = (unsigned long long)__shfl((long long)wbase, leader, WAVE);
+        if (!occ) continue;
+        /* the count stays exact past capacity (the host reports it); only
+         * the writes are bounded by the destination's size */
+        const uint64_t at = wbase + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (at >= capacity) continue;
+        okeys[at] = key;
+        for (uint32_t a = 0; a < n_aggs; a++) {
+            const ThreadAcc t = gcells[i * n_aggs + a];
+            const AccCell c{t.lo, t.hi, t.f, t.cnt};
+            ocells[at * n_aggs + a] = c;
+        }
+    }
+}
+
+static uint32_t hash_bitlen(uint64_t x)
+{
+    uint32_t n = 0;
+    while (x) { n++; x >>= 1; }
+    return n;
+}
+
+/* grow-only device buffer: reallocates when `need` elements exceed `have` */
+template <typename T>
+static int hash_grow(T *&ptr, uint64_t &have, uint64_t need)
+{
+    if (need <= have && ptr) return CSTRIPE_OK;
+    if (ptr) HIP_TRY(hipFree(ptr));
+    ptr = nullptr;
+    have = 0;
+    HIP_TRY(hipMalloc(&ptr, need * sizeof(T)));
+    have = need;
+    return CSTRIPE_OK;
+}
+
+int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                     const uint32_t *key_cols, uint32_t n_key_cols,
+                     uint64_t capacity, cstripe_hgroups *out)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    cs_gpu_state *g = s->gpu;
+    cstripe_reader *r = s->r;
+    if (!aggs || !out || !key_cols || n_aggs == 0) { cs_set_err("scan_agg_hashed: bad args"); return CSTRIPE_ERR_ARG; }
+    if (n_aggs > MAX_AGGS) { cs_set_err("too many aggs"); return CSTRIPE_ERR_ARG; }
+    if (s->preds.size() > MAX_PREDS) { cs_set_err("too many preds"); return CSTRIPE_ERR_ARG; }
+    if (n_key_cols == 0 || n_key_cols > CSTRIPE_MAX_HASH_KEY_COLS) {
+        cs_set_err("scan_agg_hashed: %u key columns (1..%d; zero keys is cstripe_scan_agg)",
+                   n_key_cols, CSTRIPE_MAX_HASH_KEY_COLS);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (capacity == 0 || capacity > CSTRIPE_MAX_HASH_GROUPS) {
+        cs_set_err("scan_agg_hashed: capacity %llu outside 1..%u",
+                   (unsigned long long)capacity, CSTRIPE_MAX_HASH_GROUPS);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (!out->partials) { cs_set_err("scan_agg_hashed: no partials destination"); return CSTRIPE_ERR_ARG; }
+
+    HashParams hp{};
+    AggParams &p = hp.base;
+    p.n_preds = (uint32_t)s->preds.size();
+    p.n_aggs = n_aggs;
+    p.n_proj = g->n_proj;
+    p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
+    if (p.tiles_per_group == 0) p.tiles_per_group = 1;
+    p.n_groups = g->n_groups;
+    for (uint32_t i = 0; i < p.n_preds; i++) {
+        const cstripe_pred &q = s->preds[i];
+        p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
+        p.preds[i].op = (uint8_t)q.op;
+        uint8_t t = r->cols[q.column].type;
+        p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
+        p.preds[i].gend = (i + 1 == p.n_preds ||
+                           s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
+        p.preds[i].ival = q.ival;
+        p.preds[i].fval = q.fval;
+    }
+    auto proj_of = [&](int32_t col) -> int {
+        if (col < 0 || col >= (int32_t)r->head.column_count) return -1;
+        return g->proj_of_col[col];
+    };
+    for (uint32_t i = 0; i < n_aggs; i++) {
+        if (aggs[i].kind > CSTRIPE_AGG_SUM_DISC_TAX_I64) { cs_set_err("agg %u: bad kind %u", i, aggs[i].kind); return CSTRIPE_ERR_ARG; }
+        p.aggs[i].kind = (uint8_t)aggs[i].kind;
+        p.aggs[i].one = aggs[i].one;
+        int pa = proj_of(aggs[i].col_a), pb = proj_of(aggs[i].col_b), pc = proj_of(aggs[i].col_c);
+        if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && pa < 0) { cs_set_err("agg %u: col_a not projected", i); return CSTRIPE_ERR_ARG; }
+        p.aggs[i].proj_a = (uint8_t)(pa < 0 ? 0 : pa);
+        p.aggs[i].proj_b = (uint8_t)(pb < 0 ? 0 : pb);
+        p.aggs[i].proj_c = (uint8_t)(pc < 0 ? 0 : pc);
+    }
+
+    /* key packing: [lo, hi] per key column from the SELECTED chunk groups'
+     * skip nodes; total bits <= 63 keeps ~0ull free as the EMPTY marker */
+    hp.n_key_cols = n_key_cols;
+    uint32_t kbits[CSTRIPE_MAX_HASH_KEY_COLS] = {0};
+    bool ktext[CSTRIPE_MAX_HASH_KEY_COLS] = {false};
+    uint32_t total_bits = 0;
+    auto set_range = [&](uint32_t k, uint32_t col, bool full, int64_t tlo, int64_t thi) {
+        int64_t lo = 0, hi = 0;
+        bool any = false;
+        for (const cs_selchunk &sc : s->sel) {
+            const csf_skipnode &nd = r->stripes[sc.stripe].nodes[col][sc.chunk].n;
+            if (nd.has_min_max) {
+                if (!any) { lo = nd.min_i; hi = nd.max_i; any = true; }
+                else { lo = std::min(lo, nd.min_i); hi = std::max(hi, nd.max_i); }
+            } else if (nd.n_present > 0) {
+                full = true;
+            }
+        }
+        if (full) { lo = tlo; hi = thi; }
+        if (hi < lo) { lo = 0; hi = 0; }
+        hp.klo[k] = lo;
+        hp.kspan[k] = (uint64_t)hi - (uint64_t)lo;
+        kbits[k] = hp.kspan[k] == ~0ull ? 65u : hash_bitlen(hp.kspan[k] + 1);
+    };
+    for (uint32_t k = 0; k < n_key_cols; k++) {
+        const uint32_t col = key_cols[k];
+        const int pj = proj_of((int32_t)col);
+        if (col >= r->head.column_count || pj < 0) { cs_set_err("scan_agg_hashed: key col %u not projected", col); return CSTRIPE_ERR_ARG; }
+        if (!out->keys[k] || !out->key_nulls[k]) { cs_set_err("scan_agg_hashed: no destination for key col %u", k); return CSTRIPE_ERR_ARG; }
+        const uint8_t t = r->cols[col].type;
+        int64_t tlo, thi;
+        switch (t) {
+            case CSTRIPE_I8:   tlo = INT8_MIN;  thi = INT8_MAX;  break;
+            case CSTRIPE_I16:  tlo = INT16_MIN; thi = INT16_MAX; break;
+            case CSTRIPE_I32:  tlo = INT32_MIN; thi = INT32_MAX; break;
+            case CSTRIPE_I64:  tlo = INT64_MIN; thi = INT64_MAX; break;
+            case CSTRIPE_TEXT: tlo = 0;         thi = (int64_t)UINT32_MAX; break;
+            default:
+                cs_set_err("scan_agg_hashed: key col %u must be I8/I16/I32/I64/TEXT", col);
+                return CSTRIPE_ERR_ARG;
+        }
+        hp.kproj[k] = (uint32_t)pj;
+        ktext[k] = t == CSTRIPE_TEXT;
+        set_range(k, col, ktext[k], tlo, thi);
+        total_bits += kbits[k];
+    }
+    if (total_bits > 63) {
+        /* beyond the 33-bit whole-slot packing: a TEXT key column may pack
+         * by its C-collation order key instead, whose [min, max] the skip
+         * nodes do record (canonical short-varlena slots only; the kernel
+         * checks every slot and the call fails otherwise) */
+        total_bits = 0;
+        for (uint32_t k = 0; k < n_key_cols; k++) {
+            if (ktext[k]) {
+                hp.klex[k] = 1;
+                set_range(k, key_cols[k], false, 0, 0xFFFFFF);
+            }
+            total_bits += kbits[k];
+        }
+    }
+    for (uint32_t k = 0, sh = 0; k < n_key_cols && total_bits <= 63; k++) {
+        hp.kshift[k] = sh;
+        sh += kbits[k];
+    }
+    if (total_bits > 63) {
+        char msg[160];
+        int w = 0;
+        for (uint32_t k = 0; k < n_key_cols; k++)
+            w += snprintf(msg + w, sizeof(msg) - (size_t)w, "%scol %u: %u bits",
+                          k ? ", " : "", key_cols[k], kbits[k]);
+        cs_set_err("scan_agg_hashed: packed key needs %u bits > 63 (%s) — key ranges "
+                   "come from the selected chunk groups' min/max", total_bits, msg);
+        return CSTRIPE_ERR_ARG;
+    }
+
+    hp.n_work = g->n_groups * p.tiles_per_group;
+    if (hp.n_work == 0) {
+        s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
+        s->last_hash_init_ms = s->last_hash_scan_ms = s->last_hash_compact_ms = 0;
+        out->n_groups = 0;
+        return CSTRIPE_OK;
+    }
+
+    uint64_t slots = 2;
+    while (slots < 2 * capacity) slots <<= 1;
+    hp.slots = slots;
+
+    /* LDS table: the largest power of two whose key words + cells fit the
+     * byte budget; CSTRIPE_HASH_LDS_SLOTS (read per call) overrides it */
+    const uint32_t slot_bytes = (uint32_t)sizeof(unsigned long long) +
+                                n_aggs * (uint32_t)sizeof(ThreadAcc);
+    uint32_t lds_max = 1;
+    while (lds_max * 2 * slot_bytes <= HASH_LDS_BUDGET) lds_max *= 2;
+    uint32_t lds_slots = lds_max;
+    if (const char *e = getenv("CSTRIPE_HASH_LDS_SLOTS")) {
+        const long v = atol(e);
+        if (v <= 0) lds_slots = 0;
+        else {
+            lds_slots = 1;
+            while ((long)lds_slots * 2 <= v && lds_slots * 2 <= lds_max) lds_slots *= 2;
+        }
+    }
+    hp.lds_slots = lds_slots;
+    const uint32_t lds_bytes = lds_slots * slot_bytes;
+
+    for (hipEvent_t &e : g->hev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    { int _rc = hash_grow(g->d_hkeys, g->hkeys_slots, slots); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_hcells, g->hcells_n, slots * n_aggs); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_hokeys, g->hokeys_n, capacity); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_hocells, g->hocells_n, capacity * n_aggs); if (_rc != CSTRIPE_OK) return _rc; }
+    if (!g->d_hcount) HIP_TRY(hipMalloc(&g->d_hcount, sizeof(unsigned long long)));
+
+    const uint32_t grid = hp.n_work < HASH_GRID ? hp.n_work : HASH_GRID;
+    const uint64_t table_blocks = (slots + AGG_BLOCK - 1) / AGG_BLOCK;
+    const uint32_t tgrid = (uint32_t)(table_blocks < 4096 ? table_blocks : 4096);
+
+    HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+    HIP_TRY(hipEventRecord(g->hev[0], g->stream));
+    { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+    HIP_TRY(hipEventRecord(g->hev[1], g->stream));
+    hipLaunchKernelGGL(hash_init_kernel, dim3(tgrid), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_hkeys, g->d_hcells, g->d_hcount, hp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->hev[2], g->stream));
+    {
+        auto launchh = [&](auto *kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(AGG_BLOCK), lds_bytes, g->stream,
+                               g->d_data, g->d_scratch, g->d_rank, g->d_groups,
+                               g->d_colloc, g->d_hkeys, g->d_hcells, g->d_error, hp);
+        };
+        if (n_aggs == 5) launchh(hash_agg_kernel<5>);
+        else if (n_aggs == 1) launchh(hash_agg_kernel<1>);
+        else if (n_aggs == 2) launchh(hash_agg_kernel<2>);
+        else launchh(hash_agg_kernel<-1>);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(g->hev[3], g->stream));
+    hipLaunchKernelGGL(hash_compact_kernel, dim3(tgrid), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_hkeys, g->d_hcells, g->d_hcount, g->d_hokeys, g->d_hocells,
+                       capacity, hp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->hev[4], g->stream));
+
+    /* the count's copy-back is the only sync before the result copy */
+    unsigned long long h_n = 0;
+    int h_err = 0;
+    HIP_TRY(hipMemcpyAsync(&h_n, g->d_hcount, sizeof(h_n), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    float ms_d = 0, ms_i = 0, ms_s = 0, ms_c = 0;
+    (void)hipEventElapsedTime(&ms_d, g->hev[0], g->hev[1]);
+    (void)hipEventElapsedTime(&ms_i, g->hev[1], g->hev[2]);
+    (void)hipEventElapsedTime(&ms_s, g->hev[2], g->hev[3]);
+    (void)hipEventElapsedTime(&ms_c, g->hev[3], g->hev[4]);
+    s->last_decode_ms = ms_d;
+    s->last_hash_init_ms = ms_i;
+    s->last_hash_scan_ms = ms_s;
+    s->last_hash_compact_ms = ms_c;
+    s->last_agg_ms = ms_i + ms_s + ms_c;
+    s->last_kernel_ms = ms_d + ms_i + ms_s + ms_c;
+    s->last_fused = 0;
+    if (h_err & 4) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    if (h_err & HASH_ERR_RANGE) {
+        cs_set_err("scan_agg_hashed: a key value lies outside its chunk's recorded min/max "
+                   "(device flag %d) — corrupt skip nodes", h_err);
+        return CSTRIPE_ERR_FORMAT;
+    }
+    if (h_err & HASH_ERR_TEXT) {
+        cs_set_err("scan_agg_hashed: a TEXT key slot is not a canonical short varlena, so the "
+                   "key tuple cannot pack by order key (whole-slot packing needs more than 63 bits)");
+        return CSTRIPE_ERR_ARG;
+    }
+    if (h_err & HASH_ERR_FULL) {
+        cs_set_err("scan_agg_hashed: more than %llu groups (hash table full; capacity %llu)",
+                   (unsigned long long)slots, (unsigned long long)capacity);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (h_err) { cs_set_err("scan_agg_hashed: device flag %d", h_err); return CSTRIPE_ERR; }
+    if (h_n > capacity) {
+        cs_set_err("scan_agg_hashed: %llu groups > capacity %llu",
+                   h_n, (unsigned long long)capacity);
+        return CSTRIPE_ERR_ARG;
+    }
+    const uint64_t n = h_n;
+    if (n == 0) { out->n_groups = 0; return CSTRIPE_OK; }
+
+    std::vector<unsigned long long> h_keys(n);
+    std::vector<AccCell> h_cells((size_t)n * n_aggs);
+    HIP_TRY(hipMemcpyAsync(h_keys.data(), g->d_hokeys, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(h_cells.data(), g->d_hocells, h_cells.size() * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+
+    /* unpack, then sort ascending by key tuple: column 0 most significant,
+     * signed compare, per column NULL last (PG ASC = NULLS LAST) */
+    auto code_of = [&](unsigned long long key, uint32_t k) -> uint64_t {
+        const uint64_t m = kbits[k] >= 64 ? ~0ull : ((1ull << kbits[k]) - 1ull);
+        return (key >> hp.kshift[k]) & m;
+    };
+    auto value_of = [&](uint64_t code, uint32_t k) -> int64_t {
+        const int64_t v = (int64_t)((uint64_t)hp.klo[k] + (code - 1));
+        return hp.klex[k] ? (int64_t)hash_text_slot((uint32_t)v) : v;
+    };
+    std::vector<int64_t> kval[CSTRIPE_MAX_HASH_KEY_COLS];
+    std::vector<uint8_t> knull[CSTRIPE_MAX_HASH_KEY_COLS];
+    for (uint32_t k = 0; k < n_key_cols; k++) {
+        kval[k].resize(n);
+        knull[k].resize(n);
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t code = code_of(h_keys[i], k);
+            knull[k][i] = code == 0 ? 1 : 0;
+            kval[k][i] = code == 0 ? 0 : value_of(code, k);
+        }
+    }
+    std::vector<uint64_t> order(n);
+    for (uint64_t i = 0; i < n; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+        for (uint32_t k = 0; k < n_key_cols; k++) {
+            if (knull[k][a] != knull[k][b]) return knull[k][a] < knull[k][b];   /* NULL last */
+            if (kval[k][a] != kval[k][b]) return kval[k][a] < kval[k][b];
+        }
+        return false;
+    });
+    for (uint64_t oi = 0; oi < n; oi++) {
+        const uint64_t i = order[oi];
+        for (uint32_t k = 0; k < n_key_cols; k++) {
+            out->key_nulls[k][oi] = knull[k][i];
+            out->keys[k][oi] = kval[k][i];
+        }
+        for (uint32_t a = 0; a < n_aggs; a++) {
+            const AccCell &c = h_cells[(size_t)i * n_aggs + a];
+            cstripe_partial o{};
+            o.count = c.cnt;
+            o.is_null = (c.cnt == 0) ? 1 : 0;
+            switch (aggs[a].kind) {
+                case CSTRIPE_AGG_COUNT_STAR:
+                case CSTRIPE_AGG_COUNT_COL:
+                    o.i128_lo = c.cnt; o.is_null = 0; break;
+                case CSTRIPE_AGG_SUM_F64:
+                case CSTRIPE_AGG_MIN_F64:
+                case CSTRIPE_AGG_MAX_F64:
+                    if (!o.is_null) o.f64 = c.f; break;
+                case CSTRIPE_AGG_MIN_I64:
+                case CSTRIPE_AGG_MAX_I64:
+                    if (!o.is_null) { o.i128_lo = c.lo; o.i128_hi = c.lo < 0 ? -1 : 0; }
+                    break;
+                default:
+                    if (!o.is_null) { o.i128_lo = c.lo; o.i128_hi = c.hi; }
+                    break;
+            }
+            out->partials[(size_t)oi * n_aggs + a] = o;
+        }
+    }
+    out->n_groups = n;
     return CSTRIPE_OK;
 }
 

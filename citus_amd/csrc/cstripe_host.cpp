@@ -1376,6 +1376,26 @@ extern "C" int cstripe_scan_last_select_ms(const cstripe_scan *s, double *mask_m
     return CSTRIPE_OK;
 }
 
+extern "C" int cstripe_scan_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs,
+                                       uint32_t n_aggs, const uint32_t *key_cols,
+                                       uint32_t n_key_cols, uint64_t capacity,
+                                       cstripe_hgroups *out)
+{
+    if (!s) { cs_set_err("scan_agg_hashed: bad args"); return CSTRIPE_ERR_ARG; }
+    /* the staged check comes first; argument checks follow it there */
+    return csgpu_agg_hashed(s, aggs, n_aggs, key_cols, n_key_cols, capacity, out);
+}
+
+extern "C" int cstripe_scan_last_hash_ms(const cstripe_scan *s, double *init_ms,
+                                         double *scan_ms, double *compact_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (init_ms) *init_ms = s->last_hash_init_ms;
+    if (scan_ms) *scan_ms = s->last_hash_scan_ms;
+    if (compact_ms) *compact_ms = s->last_hash_compact_ms;
+    return CSTRIPE_OK;
+}
+
 /* ============================ combine ============================ */
 
 static bool agg_is_count(uint32_t k)
@@ -1448,5 +1468,87 @@ extern "C" int cagg_combine(const cstripe_agg_spec *aggs, uint32_t n_aggs,
         }
         out[a] = acc;
     }
+    return CSTRIPE_OK;
+}
+
+/* the coordinator merge per group: sort every (part, group) entry by key
+ * tuple (NULL keys equal, NULL last), then cagg_combine each run of equal
+ * keys — the per-group coord_combine_agg of the reference's grouped plan
+ * (aggregate_utils.c:820-1021 under the coordinator's GroupAggregate) */
+extern "C" int cagg_combine_groups(const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                                   uint32_t n_key_cols, const cstripe_hgroups *parts,
+                                   uint32_t n_parts, cstripe_hgroups *out,
+                                   uint64_t capacity)
+{
+    if (!aggs || !out || n_aggs == 0 || (!parts && n_parts > 0) ||
+        n_key_cols == 0 || n_key_cols > CSTRIPE_MAX_HASH_KEY_COLS) {
+        cs_set_err("combine_groups: bad args");
+        return CSTRIPE_ERR_ARG;
+    }
+    for (uint32_t a = 0; a < n_aggs; a++)
+        if (aggs[a].kind > CSTRIPE_AGG_SUM_DISC_TAX_I64) { cs_set_err("combine: bad agg kind %u", aggs[a].kind); return CSTRIPE_ERR_ARG; }
+    struct Ent { uint32_t part; uint64_t g; };
+    std::vector<Ent> ents;
+    for (uint32_t p = 0; p < n_parts; p++) {
+        if (parts[p].n_groups == 0) continue;
+        if (!parts[p].partials) { cs_set_err("combine_groups: part %u has no partials", p); return CSTRIPE_ERR_ARG; }
+        for (uint32_t k = 0; k < n_key_cols; k++)
+            if (!parts[p].keys[k] || !parts[p].key_nulls[k]) { cs_set_err("combine_groups: part %u lacks key col %u", p, k); return CSTRIPE_ERR_ARG; }
+        for (uint64_t g = 0; g < parts[p].n_groups; g++) ents.push_back({p, g});
+    }
+    /* <0, 0, >0: signed compare per column, column 0 most significant,
+     * NULL last and equal to NULL */
+    auto cmp = [&](const Ent &a, const Ent &b) -> int {
+        for (uint32_t k = 0; k < n_key_cols; k++) {
+            const bool na = parts[a.part].key_nulls[k][a.g] != 0;
+            const bool nb = parts[b.part].key_nulls[k][b.g] != 0;
+            if (na || nb) {
+                if (na && nb) continue;
+                return na ? 1 : -1;
+            }
+            const int64_t va = parts[a.part].keys[k][a.g];
+            const int64_t vb = parts[b.part].keys[k][b.g];
+            if (va != vb) return va < vb ? -1 : 1;
+        }
+        return 0;
+    };
+    std::sort(ents.begin(), ents.end(),
+              [&](const Ent &a, const Ent &b) { return cmp(a, b) < 0; });
+    uint64_t needed = 0;
+    for (size_t i = 0; i < ents.size(); i++)
+        if (i == 0 || cmp(ents[i - 1], ents[i]) != 0) needed++;
+    if (needed > capacity) {
+        out->n_groups = needed;
+        cs_set_err("combine_groups: %llu groups > capacity %llu",
+                   (unsigned long long)needed, (unsigned long long)capacity);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (needed > 0) {
+        if (!out->partials) { cs_set_err("combine_groups: no partials destination"); return CSTRIPE_ERR_ARG; }
+        for (uint32_t k = 0; k < n_key_cols; k++)
+            if (!out->keys[k] || !out->key_nulls[k]) { cs_set_err("combine_groups: no destination for key col %u", k); return CSTRIPE_ERR_ARG; }
+    }
+    std::vector<cstripe_partial> run;
+    uint64_t og = 0;
+    for (size_t i = 0; i < ents.size();) {
+        size_t j = i + 1;
+        while (j < ents.size() && cmp(ents[i], ents[j]) == 0) j++;
+        run.clear();
+        for (size_t e = i; e < j; e++) {
+            const cstripe_partial *src = parts[ents[e].part].partials + ents[e].g * n_aggs;
+            run.insert(run.end(), src, src + n_aggs);
+        }
+        int rc = cagg_combine(aggs, n_aggs, run.data(), (uint32_t)(j - i),
+                              out->partials + og * n_aggs);
+        if (rc != CSTRIPE_OK) return rc;
+        for (uint32_t k = 0; k < n_key_cols; k++) {
+            const bool nul = parts[ents[i].part].key_nulls[k][ents[i].g] != 0;
+            out->key_nulls[k][og] = nul ? 1 : 0;
+            out->keys[k][og] = nul ? 0 : parts[ents[i].part].keys[k][ents[i].g];
+        }
+        og++;
+        i = j;
+    }
+    out->n_groups = og;
     return CSTRIPE_OK;
 }

@@ -71,6 +71,9 @@ struct cstripe_scan {
     double last_select_mask_ms = 0.0;     /* scan_select per-kernel split */
     double last_select_offsets_ms = 0.0;
     double last_select_emit_ms = 0.0;
+    double last_hash_init_ms = 0.0;       /* scan_agg_hashed per-kernel split */
+    double last_hash_scan_ms = 0.0;
+    double last_hash_compact_ms = 0.0;
     /* random-access read cache (the reference keeps the current stripe
      * open across ColumnarReadRowByRowNumber calls the same way) */
     int64_t rr_gi = -1;
@@ -101,6 +104,11 @@ int  csgpu_fetch_batch(cstripe_scan *s, uint32_t gi, cstripe_batch *batch);
 int  csgpu_select_count(cstripe_scan *s, uint64_t *n_rows);
 int  csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
                   int dst_on_device);
+/* hashed GROUP BY (table init -> scan + hash aggregate -> compaction);
+ * the device tables hang off the scan and grow on demand */
+int  csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                      const uint32_t *key_cols, uint32_t n_key_cols,
+                      uint64_t capacity, cstripe_hgroups *out);
 
 /* device write path: one chunk's columns compressed on the GPU (canonical
  * parses where the data fits, raw copy-back otherwise) */

@@ -396,6 +396,81 @@ int cstripe_scan_select(cstripe_scan *s, cstripe_rows *out,
 int cstripe_scan_last_select_ms(const cstripe_scan *s, double *mask_ms,
                                 double *offsets_ms, double *emit_ms);
 
+/* ---- hashed GROUP BY (device hash aggregate over integer keys) ----
+ * The worker side of the reference's general grouped plan: HashAggregate
+ * over ColumnarScan, one partial row per group, then a per-group coordinator
+ * merge (multi_explain.out:80-82, multi_logical_optimizer.c:1807-1885,
+ * aggregate_utils.c:820-1021). Unlike cstripe_scan_agg_grouped (Q1 shape,
+ * <= 64 groups of char(1) keys) the group count is bounded only by the
+ * caller's capacity. Caller provides every destination; capacity is in
+ * groups. */
+#define CSTRIPE_MAX_HASH_KEY_COLS 4
+#define CSTRIPE_MAX_HASH_GROUPS   (1u << 24)
+
+typedef struct cstripe_hgroups {
+    uint64_t         n_groups;                               /* out */
+    int64_t         *keys[CSTRIPE_MAX_HASH_KEY_COLS];        /* in: capacity entries each (first n_key_cols used) */
+    uint8_t         *key_nulls[CSTRIPE_MAX_HASH_KEY_COLS];   /* in: capacity bytes each; 1 = NULL key */
+    cstripe_partial *partials;                               /* in: capacity * n_aggs, [g*n_aggs + a] */
+} cstripe_hgroups;
+
+/* cstripe_scan_agg_hashed:
+ *  - Keys: 1..CSTRIPE_MAX_HASH_KEY_COLS columns of type I8/I16/I32/I64/TEXT.
+ *    F32/F64 keys, zero key columns (that is cstripe_scan_agg), more than
+ *    4, or a key column that is not projected return CSTRIPE_ERR_ARG. A key
+ *    value comes back sign-extended in keys[k][g]; TEXT returns the whole
+ *    4-byte slot zero-extended (TEXT groups by slot here, not by first
+ *    payload byte — for char(1) the two are the same). NULL keys form their
+ *    own group, like the reference's HashAggregate (grouping treats NULLs
+ *    as equal): key_nulls[k][g] = 1, keys[k][g] = 0.
+ *  - Filter, aggregates, NULL operands, PG NaN order, is_null, COUNT never
+ *    null: exactly as cstripe_scan_agg_grouped — the same 11 agg kinds, the
+ *    same accumulator-to-partial conversion, int128 sums exact. Chunk groups
+ *    removed by min/max pruning contribute nothing.
+ *  - Order: each distinct key tuple appears exactly once; groups are sorted
+ *    ascending by key tuple, column 0 most significant, signed compare, per
+ *    column NULL last (PG's ASC defaults to NULLS LAST). Identical on every
+ *    call.
+ *  - Capacity: 1..CSTRIPE_MAX_HASH_GROUPS, else CSTRIPE_ERR_ARG. The device
+ *    table has slots = max(2, next_pow2(2*capacity)). More groups than
+ *    capacity returns CSTRIPE_ERR_ARG and writes nothing: the message names
+ *    the exact group count and the capacity when the table did not fill,
+ *    and says "more than <slots> groups" when it did.
+ *  - Key packing (the supported domain): the device key is ONE 64-bit word.
+ *    Per key column the library takes [lo, hi] from the skip nodes
+ *    (min/max) of the scan's SELECTED chunk groups; a selected chunk with
+ *    present values and no min/max widens that column to its type's full
+ *    range; TEXT always uses the slot as u32, 0..2^32-1 (its skip-node
+ *    min/max are order keys, not slots). A column's code is 0 for NULL,
+ *    else 1 + (v - lo), in bitlen(hi - lo + 1) bits. The bits of all key
+ *    columns must total <= 63; wider key tuples return CSTRIPE_ERR_ARG (the
+ *    message names each column's bits) — not pushdownable through this ABI,
+ *    like an over-wide CNF. One extension past whole-slot TEXT packing:
+ *    when the total exceeds 63 bits and TEXT key columns are among them
+ *    (two char(1) flags are already 66), those columns pack by their
+ *    C-collation order key instead, whose [min, max] the skip nodes do
+ *    record; keys still come back as slots, sorted by slot value. That
+ *    form needs canonical short-varlena slots (header = payload length,
+ *    zero padding); the kernel checks every slot and any other slot fails
+ *    the call with CSTRIPE_ERR_ARG. A value outside [lo, hi] (a file whose skip
+ *    nodes lie) surfaces as CSTRIPE_ERR_FORMAT, never as a wrong group.
+ *  - Needs a staged scan (CSTRIPE_ERR_NOGPU otherwise; checked first). Zero
+ *    selected chunk groups or zero passing rows: CSTRIPE_OK, n_groups = 0.
+ *  - Re-invocable, and may be interleaved with scan_agg, scan_agg_grouped,
+ *    scan_select, next_batch and read_row on the same scan without changing
+ *    any of their results. cstripe_scan_last_kernel_ms /
+ *    cstripe_scan_last_decode_kernel_ms then report the last hashed call;
+ *    cstripe_scan_last_hash_ms splits the device time per kernel (table
+ *    init, scan + hash aggregate, compaction); any out pointer may be NULL.
+ *  - CSTRIPE_HASH_LDS_SLOTS (environment, read per call) overrides the
+ *    per-block LDS table's slot count: 0 = no LDS table, a small power of
+ *    two forces overflow into the global table. Results do not depend on
+ *    it. */
+int cstripe_scan_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                            const uint32_t *key_cols, uint32_t n_key_cols,
+                            uint64_t capacity, cstripe_hgroups *out);
+int cstripe_scan_last_hash_ms(const cstripe_scan *s, double *init_ms, double *scan_ms, double *compact_ms);
+
 /* 1 when the last cstripe_scan_agg ran the fused decode+filter+aggregate
  * kernel (no scratch round trip), 0 for the two-kernel path */
 int cstripe_scan_last_fused(const cstripe_scan *s);
@@ -414,6 +489,17 @@ double cstripe_scan_last_agg_kernel_ms(const cstripe_scan *s);
 int cagg_combine(const cstripe_agg_spec *aggs, uint32_t n_aggs,
                  const cstripe_partial *parts, uint32_t n_parts,
                  cstripe_partial *out);
+
+/* The coordinator merge per group (host C, no GPU): the union of the key
+ * tuples of all parts; for each key, cagg_combine over the entries that hold
+ * it. Inputs may be in any order and a part may hold a key more than once
+ * (those merge too); NULL keys compare equal. Output is sorted like
+ * cstripe_scan_agg_hashed's. More than `capacity` result groups returns
+ * CSTRIPE_ERR_ARG with the needed count in out->n_groups and writes nothing
+ * else. */
+int cagg_combine_groups(const cstripe_agg_spec *aggs, uint32_t n_aggs, uint32_t n_key_cols,
+                        const cstripe_hgroups *parts, uint32_t n_parts,
+                        cstripe_hgroups *out, uint64_t capacity);
 
 /* =================== RCCL combine (device collective) ===================
  * The north star replaces the coordinator merge with a collective over
