@@ -40,6 +40,9 @@ _lib = C.CDLL(_LIB_PATH)
 
 # ---- enums (include/cstripe.h) ----
 I8, I16, I32, I64, F32, F64, TEXT = 1, 2, 3, 4, 5, 6, 7
+VARTEXT = 8                      # general variable-length text (device dictionary)
+VARTEXT_MAX_LEN = 65535
+VARTEXT_MAX_DISTINCT = 1 << 20
 COMP_NONE, COMP_PGLZ, COMP_LZ4, COMP_ZSTD = 0, 1, 2, 3
 PRED_LT, PRED_LE, PRED_GT, PRED_GE, PRED_EQ, PRED_NE = range(6)
 (AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM_I64, AGG_SUM_F64,
@@ -68,6 +71,14 @@ class Pred(C.Structure):
     _fields_ = [("column", C.c_uint32), ("op", C.c_uint32),
                 ("ival", C.c_int64), ("fval", C.c_double),
                 ("or_group", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class VarTextIn(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("bytes", C.c_void_p)]
+
+
+class TextConst(C.Structure):
+    _fields_ = [("data", C.c_char_p), ("len", C.c_uint32)]
 
 
 class AggSpec(C.Structure):
@@ -162,6 +173,7 @@ _write_begin = _sig("cstripe_write_begin", C.c_void_p,
 _write_rows = _sig("cstripe_write_rows", C.c_int,
                    [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
 _write_end = _sig("cstripe_write_end", C.c_int, [C.c_void_p])
+_write_abort = _sig("cstripe_write_abort", None, [C.c_void_p])
 _write_rows_device = _sig("cstripe_write_rows_device", C.c_int,
                           [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)])
 _open = _sig("cstripe_open", C.c_void_p, [C.c_char_p])
@@ -172,6 +184,17 @@ _stripe_count = _sig("cstripe_stripe_count", C.c_uint32, [C.c_void_p])
 _column_def = _sig("cstripe_column_def", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ColDef)])
 _scan_begin = _sig("cstripe_scan_begin", C.c_void_p,
                    [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32])
+_scan_begin_ex = _sig("cstripe_scan_begin_ex", C.c_void_p,
+                      [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32,
+                       C.POINTER(TextConst), C.c_uint32])
+_vartext_validate = _sig("cstripe_vartext_validate", C.c_int,
+                         [C.c_char_p, C.c_uint64, C.c_uint32])
+_text_dict = _sig("cstripe_scan_text_dict", C.c_int,
+                  [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                   C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint8))])
+_last_text_ms = _sig("cstripe_scan_last_text_ms", C.c_int,
+                     [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                      C.POINTER(C.c_double), C.POINTER(C.c_double)])
 _scan_end = _sig("cstripe_scan_end", None, [C.c_void_p])
 _filtered = _sig("cstripe_scan_chunk_groups_filtered", C.c_int64, [C.c_void_p])
 _gpu_stage = _sig("cstripe_gpu_stage", C.c_int, [C.c_void_p, C.c_int])
@@ -299,27 +322,85 @@ def make_coldefs(defs):
     return arr
 
 
+def vartext_pack(values):
+    """(offsets uint64[n+1], bytes uint8[], nulls uint8[n] or None) for a
+    sequence of bytes / str / None — the cstripe_vartext_in form of a VARTEXT
+    column. str values are stored as UTF-8."""
+    import numpy as np
+    enc = [b"" if v is None else (v.encode() if isinstance(v, str) else bytes(v))
+           for v in values]
+    offs = np.zeros(len(enc) + 1, dtype=np.uint64)
+    if enc:
+        offs[1:] = np.cumsum([len(b) for b in enc], dtype=np.uint64)
+    data = np.frombuffer(b"".join(enc), dtype=np.uint8)
+    nulls = None
+    if any(v is None for v in values):
+        nulls = np.array([1 if v is None else 0 for v in values], dtype=np.uint8)
+    return offs, data, nulls
+
+
+def vartext_validate(stream, n_values):
+    """cstripe_vartext_validate: OK when exactly n_values varlena datums tile
+    the stream, ERR_FORMAT otherwise (host only)."""
+    stream = bytes(stream)
+    return _vartext_validate(stream, len(stream), n_values)
+
+
 def write_table(path, defs, columns, nulls=None, **opt_kw):
     """Write numpy columns to a stripe file. columns: list of np arrays
-    (dtype matching coldef types); nulls: optional list of uint8 arrays."""
+    (dtype matching coldef types); nulls: optional list of uint8 arrays.
+    A VARTEXT column is a list of bytes / str / None (None = NULL, merged
+    with that column's nulls entry when both are given), or an
+    (offsets uint64[n+1], bytes uint8[]) pair of numpy arrays."""
     import numpy as np
     opts = default_options(**opt_kw)
     cols = make_coldefs(defs)
+    n = None
+    vals = (C.c_void_p * len(defs))()
+    keep = []
+    text_nulls = {}
+    for i, a in enumerate(columns):
+        if defs[i][1] == VARTEXT:
+            if isinstance(a, tuple):
+                offs, data = a
+            else:
+                offs, data, tn = vartext_pack(a)
+                if tn is not None:
+                    text_nulls[i] = tn
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            vt = VarTextIn(offs.ctypes.data, data.ctypes.data if data.size else None)
+            keep += [offs, data, vt]
+            vals[i] = C.addressof(vt)
+            rows = len(offs) - 1
+        else:
+            a = np.ascontiguousarray(a)
+            columns[i] = a
+            vals[i] = a.ctypes.data_as(C.c_void_p).value
+            rows = len(a)
+        n = rows if n is None else n
+        if rows != n:
+            raise CStripeError(f"write_table: column {i} has {rows} rows, column 0 has {n}")
+    nl = None
+    if nulls is not None or text_nulls:
+        nl = (C.c_void_p * len(defs))()
+        for i in range(len(defs)):
+            a = nulls[i] if nulls is not None else None
+            if i in text_nulls:
+                a = text_nulls[i] if a is None else \
+                    (np.asarray(a, dtype=np.uint8) | text_nulls[i])
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint8)
+                keep.append(a)
+                nl[i] = a.ctypes.data_as(C.c_void_p).value
     w = _write_begin(path.encode(), cols, len(defs), C.byref(opts))
     if not w:
         raise CStripeError("write_begin: " + errmsg())
-    n = len(columns[0])
-    vals = (C.c_void_p * len(defs))()
-    for i, a in enumerate(columns):
-        a = np.ascontiguousarray(a)
-        columns[i] = a
-        vals[i] = a.ctypes.data_as(C.c_void_p).value
-    nl = None
-    if nulls is not None:
-        nl = (C.c_void_p * len(defs))()
-        for i, a in enumerate(nulls):
-            nl[i] = a.ctypes.data_as(C.c_void_p).value if a is not None else None
-    _check(_write_rows(w, n, vals, nl), "write_rows")
+    rc = _write_rows(w, n, vals, nl)
+    if rc != OK:
+        msg = errmsg()
+        _write_abort(w)
+        raise CStripeError(f"write_rows failed (rc={rc}): {msg}")
     _check(_write_end(w), "write_end")
 
 
@@ -435,19 +516,39 @@ def make_preds(preds):
     """preds: (column, op, value) or (column, op, value, or_group) tuples.
     A nonzero or_group groups predicates into a disjunction (CNF; see
     include/cstripe.h)."""
+    return make_preds_ex(preds)[0]
+
+
+def make_preds_ex(preds):
+    """make_preds plus the string constants: a bytes / str value (a VARTEXT
+    predicate) becomes an index into the returned cstripe_text_const array.
+    Returns (Pred array, TextConst array or None, n_text_consts)."""
     arr = (Pred * max(1, len(preds)))()
+    texts = []
     for i, p in enumerate(preds):
         arr[i].column = p[0]
         arr[i].op = p[1]
         v = p[2]
-        if isinstance(v, float):
+        if isinstance(v, (bytes, bytearray, str)):
+            b = v.encode() if isinstance(v, str) else bytes(v)
+            arr[i].ival = len(texts)
+            arr[i].fval = 0.0
+            texts.append(b)
+        elif isinstance(v, float):
             arr[i].fval = v
             arr[i].ival = 0
         else:
             arr[i].ival = int(v)
             arr[i].fval = 0.0
         arr[i].or_group = p[3] if len(p) > 3 else 0
-    return arr
+    if not texts:
+        return arr, None, 0
+    tc = (TextConst * len(texts))()
+    for i, b in enumerate(texts):
+        tc[i].data = b            # c_char_p keeps a reference to the bytes
+        tc[i].len = len(b)
+    tc._keep = texts
+    return arr, tc, len(texts)
 
 
 def agg_cols_mask(aggs):
@@ -531,8 +632,12 @@ def combine_groups(aggs, n_key_cols, results, capacity=None):
 
 class Scan:
     def __init__(self, reader, cols_mask, preds):
-        self._preds = make_preds(preds)
-        self._h = _scan_begin(reader._h, cols_mask, self._preds, len(preds))
+        self._preds, self._texts, n_texts = make_preds_ex(preds)
+        if n_texts:     # string constants: VARTEXT predicates
+            self._h = _scan_begin_ex(reader._h, cols_mask, self._preds, len(preds),
+                                     self._texts, n_texts)
+        else:
+            self._h = _scan_begin(reader._h, cols_mask, self._preds, len(preds))
         if not self._h:
             raise CStripeError("scan_begin: " + errmsg())
         self.reader = reader
@@ -584,6 +689,38 @@ class Scan:
         _check(_gpu_stage(self._h, device), "gpu_stage")
         self._device = device
 
+    def text_dict(self, col):
+        """The sorted per-scan dictionary of a projected VARTEXT column of a
+        staged scan, as a list of bytes: rank i in select / agg_hashed
+        results of this scan means entry i (memcmp order)."""
+        import numpy as np
+        n = C.c_uint32()
+        offs = C.POINTER(C.c_uint64)()
+        data = C.POINTER(C.c_uint8)()
+        _check(_text_dict(self._h, col, C.byref(n), C.byref(offs), C.byref(data)),
+               "scan_text_dict")
+        o = np.ctypeslib.as_array(offs, shape=(n.value + 1,)).copy()
+        total = int(o[-1])
+        blob = C.string_at(data, total) if total else b""
+        return [blob[int(o[i]):int(o[i + 1])] for i in range(n.value)]
+
+    def last_text_ms(self):
+        """(decode, walk, dict, remap) device ms of the last stage()'s
+        VARTEXT dictionary build; zeros when no text column is projected"""
+        d, w, t, m = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        _check(_last_text_ms(self._h, C.byref(d), C.byref(w), C.byref(t), C.byref(m)),
+               "scan_last_text_ms")
+        return d.value, w.value, t.value, m.value
+
+    def _decode_ranks(self, col, ranks, nulls):
+        """object array of bytes / None from a VARTEXT column's ranks"""
+        import numpy as np
+        d = self.text_dict(col)
+        out = np.empty(len(ranks), dtype=object)
+        for i in range(len(ranks)):
+            out[i] = None if (nulls is not None and nulls[i]) else d[int(ranks[i])]
+        return out
+
     def agg(self, aggs):
         """aggs: list of (kind, col_a[, col_b[, col_c[, one]]]) -> [Partial]"""
         arr = make_aggs(aggs)
@@ -604,19 +741,27 @@ class Scan:
             res[key] = [out[g * len(aggs) + a] for a in range(len(aggs))]
         return res
 
-    def agg_hashed(self, aggs, key_cols, capacity):
+    def agg_hashed(self, aggs, key_cols, capacity, decode_text=False):
         """Hashed GROUP BY (cstripe_scan_agg_hashed) over 1..4 integer/TEXT
         key columns, at most `capacity` groups. Returns {"n_groups",
         "keys": [int64 array per key col], "key_nulls": [uint8 arrays],
         "partials": structured array (n_groups, n_aggs) of partial_dtype()},
-        sorted ascending by key tuple, NULL keys last."""
+        sorted ascending by key tuple, NULL keys last. A VARTEXT key comes
+        back as its dictionary rank; decode_text=True adds "text_keys":
+        {k: object array of bytes / None} for those key positions."""
         arr = make_aggs(aggs)
         kc = (C.c_uint32 * max(1, len(key_cols)))(*key_cols)
         bufs, hg = _alloc_hgroups(len(key_cols), len(aggs),
                                   min(max(int(capacity), 1), MAX_HASH_GROUPS))
         _check(_scan_agg_hashed(self._h, arr, len(aggs), kc, len(key_cols),
                                 capacity, C.byref(hg)), "scan_agg_hashed")
-        return _hgroups_result(bufs, hg.n_groups)
+        res = _hgroups_result(bufs, hg.n_groups)
+        if decode_text:
+            res["text_keys"] = {
+                k: self._decode_ranks(c, res["keys"][k], res["key_nulls"][k])
+                for k, c in enumerate(key_cols)
+                if self._reader.column_def(c)[1] == VARTEXT}
+        return res
 
     @property
     def last_hash_ms(self):
@@ -660,6 +805,8 @@ class Scan:
         for c in range(ncols):
             if not (self._mask >> c) & 1:
                 continue
+            if r.column_def(c)[1] == VARTEXT:
+                continue        # no row access to variable-length text
             a = np.zeros(1, dtype=DT[r.column_def(c)[1]])
             bufs[c] = a
             vp[c] = a.ctypes.data_as(C.c_void_p).value
@@ -686,7 +833,7 @@ class Scan:
         return m.value, o.value, e.value
 
     def select(self, cols=None, want_nulls=True, want_row_numbers=True,
-               device=False):
+               device=False, decode_text=False):
         """Filtered row materialisation (cstripe_scan_select): the rows that
         pass the scan's predicates, compacted on device, in scan order.
         cols: column indices to return (None = every projected column).
@@ -695,7 +842,10 @@ class Scan:
         wanted. Host mode returns numpy arrays (read_row's dtype map);
         device=True returns torch tensors on the scan's device (ints and
         floats by width, TEXT as int32 bit patterns, row numbers int64)
-        whose data_ptr() can go straight into write_table_device."""
+        whose data_ptr() can go straight into write_table_device.
+        A VARTEXT column comes back as int32 dictionary ranks (text_dict);
+        decode_text=True (host mode, needs want_nulls) adds "text":
+        {col: object array of bytes / None}."""
         r = self._reader
         ncols = r.column_count
         if cols is None:
@@ -715,7 +865,7 @@ class Scan:
                                else torch.cuda.current_device())
             DT = {1: torch.int8, 2: torch.int16, 3: torch.int32,
                   4: torch.int64, 5: torch.float32, 6: torch.float64,
-                  7: torch.int32}
+                  7: torch.int32, 8: torch.int32}
 
             def alloc(dt):
                 return torch.empty(cap, dtype=dt, device=dev)
@@ -727,7 +877,7 @@ class Scan:
         else:
             import numpy as np
             DT = {1: np.int8, 2: np.int16, 3: np.int32, 4: np.int64,
-                  5: np.float32, 6: np.float64, 7: np.uint32}
+                  5: np.float32, 6: np.float64, 7: np.uint32, 8: np.int32}
 
             def alloc(dt):
                 return np.zeros(cap, dtype=dt)
@@ -759,10 +909,16 @@ class Scan:
         self.select_profile = {"decode_ms": d_ms, "mask_ms": m_ms,
                                "offsets_ms": o_ms, "emit_ms": e_ms,
                                "total_ms": d_ms + m_ms + o_ms + e_ms}
-        return {"n_rows": k,
-                "row_numbers": None if rn is None else rn[:k],
-                "values": {c: a[:k] for c, a in vals.items()},
-                "nulls": {c: a[:k] for c, a in nulls.items()}}
+        res = {"n_rows": k,
+               "row_numbers": None if rn is None else rn[:k],
+               "values": {c: a[:k] for c, a in vals.items()},
+               "nulls": {c: a[:k] for c, a in nulls.items()}}
+        if decode_text:
+            if device or not want_nulls:
+                raise CStripeError("select: decode_text needs host mode and want_nulls")
+            res["text"] = {c: self._decode_ranks(c, res["values"][c], res["nulls"][c])
+                           for c in cols if types[c] == VARTEXT}
+        return res
 
     def rewind(self):
         _check(_rewind(self._h), "rewind")

@@ -26,6 +26,7 @@
 #include "pglz.h"
 #include "zstd_r.h"
 #include "lz4_enc.h"
+#include "vartext.h"
 
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -185,6 +186,10 @@ struct cs_gpu_state {
     /* host-side mirror for next_batch (exists read from mmap) */
     std::vector<uint64_t> scratch_off;  /* per (sel,proj): decomp offset */
     std::vector<ColLoc> colloc_host;
+    /* VARTEXT predicates translated at stage into integer atoms over the
+     * column's dictionary ranks, parallel to scan->preds (fill_preds) */
+    std::vector<uint8_t> tpred_op;
+    std::vector<int64_t> tpred_ival;
 };
 
 /* ---------------- error helper ---------------- */
@@ -3078,10 +3083,39 @@ uint64_t csgpu_staged_bytes(const cstripe_scan *s)
     return s->gpu ? s->gpu->data_bytes : 0;
 }
 
+/* temporary device buffers and events of one VARTEXT dictionary build
+ * (vartext_build, below launch_decode); freed when the stage call returns */
+struct VtTemps {
+    void *bufs[16] = {nullptr};
+    uint32_t n_bufs = 0;
+    hipEvent_t ev[8] = {nullptr};
+    template <typename T>
+    hipError_t alloc(T *&p, uint64_t bytes)
+    {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+        if (e == hipSuccess) { bufs[n_bufs++] = q; p = (T *)q; }
+        return e;
+    }
+    /* per-column buffers go back early; the rest at release() */
+    void free_from(uint32_t first)
+    {
+        while (n_bufs > first) { hipError_t e = hipFree(bufs[--n_bufs]); (void)e; }
+    }
+    void release()
+    {
+        free_from(0);
+        for (hipEvent_t &e : ev)
+            if (e) { hipError_t r = hipEventDestroy(e); (void)r; e = nullptr; }
+    }
+};
+static int vartext_build(cstripe_scan *s, VtTemps &vt);
+
 int csgpu_stage(cstripe_scan *s, int device_id)
 {
     if (!cstripe_gpu_available()) { cs_set_err("no HIP device visible — the cstripe GPU path requires an MI355X (no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
     if (s->gpu) csgpu_release(s);
+    s->text_dicts.clear();
 
     cstripe_reader *r = s->r;
     auto *g = new cs_gpu_state();
@@ -3112,6 +3146,9 @@ int csgpu_stage(cstripe_scan *s, int device_id)
     uint64_t data_bytes = 0, scratch_bytes = 0, rank_words = 0;
     uint32_t n_segs = 0, n_zsegs = 0;
     bool zstd_host = false;
+    bool any_vartext = false;
+    for (uint32_t c = 0; c < r->head.column_count; c++)
+        any_vartext |= g->proj_of_col[c] >= 0 && r->cols[c].type == CSTRIPE_VARTEXT;
     for (const auto &sc : s->sel) {
         const cs_stripe_info &st = r->stripes[sc.stripe];
         uint32_t rows = st.group_rows[sc.chunk];
@@ -3119,6 +3156,16 @@ int csgpu_stage(cstripe_scan *s, int device_id)
             if (g->proj_of_col[c] < 0) continue;
             const cs_skipnode &nd = st.nodes[c][sc.chunk];
             data_bytes = align_up(data_bytes, 8) + align_up((rows + 7) / 8, 8); /* exists, 8B padded */
+            if (r->cols[c].type == CSTRIPE_VARTEXT) {
+                /* read as int32 dictionary ranks: n_present entries in a
+                 * scratch region no decode segment writes (vartext_build);
+                 * the byte stream itself is staged to temporary buffers */
+                scratch_bytes = align_up(scratch_bytes, 16) + align_up((uint64_t)nd.n.n_present * 4, 16);
+                any_vartext = true;
+                if (nd.n.n_present != nd.n.row_count)
+                    rank_words += (rows + 63) / 64;
+                continue;
+            }
             const bool canon = cs_node_canon(nd);
             bool zr_dev = !canon && nd.n.comp_type == CSTRIPE_COMP_ZSTD;
             if (zr_dev)
@@ -3147,6 +3194,10 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         }
     }
     (void)zstd_host;
+    if (any_vartext)
+        scratch_bytes += 64;        /* the R-row windowed loads of the dense
+                                     * kernels reach up to R-1 entries past a
+                                     * rank array's end */
 
     uint32_t tiles_pg = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
     if (tiles_pg == 0) tiles_pg = 1;
@@ -3245,6 +3296,24 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 cl.flags |= 2;
             }
             if (!(cl.flags & 2)) g->all_dense = false;
+            if (r->cols[c].type == CSTRIPE_VARTEXT) {
+                /* the column reads as I32 ranks in scratch, dense or sparse
+                 * through the rank table above; vartext_build fills the
+                 * region after the uploads. Never canonical or fusable, and
+                 * launch_decode has nothing to do for it (col_scratch 0). */
+                cl.type = CSTRIPE_I32;
+                cl.width = 4;
+                cl.flags |= 1;
+                spos = align_up(spos, 16);
+                cl.val_off = spos;
+                spos += align_up((uint64_t)nd.n.n_present * 4, 16);
+                g->fusable = false;
+                g->fusable_mixed = false;
+                g->all_canonP = false;
+                col_g256[pj] = 0;
+                h_colloc[(uint64_t)gi * n_proj + pj] = cl;
+                continue;
+            }
             {
                 const cs_skipnode &nd2 = st.nodes[c][sc.chunk];
                 const bool cp = nd2.n.comp_type == CSTRIPE_COMP_LZ4 &&
@@ -3513,15 +3582,41 @@ int csgpu_stage(cstripe_scan *s, int device_id)
     }
     HIP_TRY(hipStreamSynchronize(g->stream));
     g->colloc_host = h_colloc;
+    s->text_dicts.clear();
+    s->last_text_decode_ms = s->last_text_walk_ms = 0;
+    s->last_text_dict_ms = s->last_text_remap_ms = 0;
+    g->tpred_op.assign(s->preds.size(), 0);
+    g->tpred_ival.assign(s->preds.size(), 0);
+    if (any_vartext) {
+        VtTemps vt;
+        int rc = vartext_build(s, vt);
+        vt.release();
+        if (rc != CSTRIPE_OK) {
+            /* the message is set; the scan is left unstaged */
+            csgpu_release(s);
+            s->text_dicts.clear();
+            return rc;
+        }
+    }
     return CSTRIPE_OK;
 }
 
 /* launch the decode grid: LDS-staged variant when every segment fits the
  * 64 KiB budget (writer default 8 KiB segments -> ~9 waves/CU), else the
  * global-memory fallback */
-static int launch_decode(cs_gpu_state *g)
+struct DecodeJob {
+    const uint8_t *data;        /* staged compressed bytes (SegDesc.src_off) */
+    uint8_t *out;               /* decode target (SegDesc.dst_off) */
+    const SegDesc *segs;        /* LZ4 segments */
+    uint32_t n_segs, max_seg_comp, max_seg_dlen;
+    bool segs_16aligned;
+    const SegDesc *zsegs;       /* restricted-zstd frames */
+    uint32_t n_zsegs, max_zseg_comp, max_zseg_dlen;
+};
+
+static int launch_decode_job(cs_gpu_state *g, const DecodeJob &j)
 {
-    if (g->n_zsegs > 0) {
+    if (j.n_zsegs > 0) {
         /* CSTRIPE_ZR_VARIANT: 0 = force global kernel (A/B knob), default =
          * LDS-staged when the largest frame fits the budget */
         const char *zv = getenv("CSTRIPE_ZR_VARIANT");
@@ -3533,62 +3628,653 @@ static int launch_decode(cs_gpu_state *g)
          * equal-progress lanes hit bank (l*stride/4 + c) mod 64 — an odd
          * dword stride makes those 64 distinct banks (even residues conflict
          * 2-32 way; same rule as the lz4 lane kernel's 276/532/1044) */
-        uint32_t stride = ((g->max_zseg_comp + 8 + 3) & ~3u) + 4;
+        uint32_t stride = ((j.max_zseg_comp + 8 + 3) & ~3u) + 4;
         if (((stride / 4) & 1) == 0) stride += 4;
-        uint32_t ostride = ((g->max_zseg_dlen + 3) & ~3u) + 4;
+        uint32_t ostride = ((j.max_zseg_dlen + 3) & ~3u) + 4;
         if (((ostride / 4) & 1) == 0) ostride += 4;
-        const uint32_t grid = (g->n_zsegs + ZR_LDS_BLOCK - 1) / ZR_LDS_BLOCK;
+        const uint32_t grid = (j.n_zsegs + ZR_LDS_BLOCK - 1) / ZR_LDS_BLOCK;
         const size_t lds1 = (size_t)ZR_LDS_BLOCK * stride + sizeof(zr_dtables);
         const size_t lds2 = lds1 + (size_t)ZR_LDS_BLOCK * ostride;
         if ((force == -1 || force >= 2) && lds2 <= 152 * 1024) {
             hipLaunchKernelGGL(zr_decode_lds2_kernel, dim3(grid), dim3(ZR_LDS_BLOCK),
                                lds2, g->stream,
-                               g->d_data, g->d_scratch, g->d_zsegs, g->n_zsegs,
+                               j.data, j.out, j.zsegs, j.n_zsegs,
                                stride, ostride, g->d_zrtab, g->d_error);
         } else if (force != 0 && lds1 <= 152 * 1024) {
             hipLaunchKernelGGL(zr_decode_lds_kernel, dim3(grid), dim3(ZR_LDS_BLOCK),
                                lds1, g->stream,
-                               g->d_data, g->d_scratch, g->d_zsegs, g->n_zsegs,
+                               j.data, j.out, j.zsegs, j.n_zsegs,
                                stride, g->d_zrtab, g->d_error);
         } else {
-            const uint32_t grid = (g->n_zsegs + 255) / 256;
+            const uint32_t grid = (j.n_zsegs + 255) / 256;
             hipLaunchKernelGGL(zr_decode_kernel, dim3(grid), dim3(256), 0, g->stream,
-                               g->d_data, g->d_scratch, g->d_zsegs, g->n_zsegs,
+                               j.data, j.out, j.zsegs, j.n_zsegs,
                                g->d_zrtab, g->d_error);
         }
         HIP_TRY(hipGetLastError());
     }
-    if (g->n_segs == 0) return CSTRIPE_OK;
+    if (j.n_segs == 0) return CSTRIPE_OK;
     /* lane-parallel path for micro-segments (one lane per segment).
      * stride: 16 B-multiple, (stride/4)%64 != 0 so equal-progress lanes land
      * on different banks; LDS/wave = 64*stride -> waves/CU 9 / 4 / 2. */
-    if (g->segs_16aligned && g->max_seg_dlen <= 1039) {
+    if (j.segs_16aligned && j.max_seg_dlen <= 1039) {
         uint32_t block, stride;
-        if (g->max_seg_dlen <= 275)      { block = 256; stride = 276; }
-        else if (g->max_seg_dlen <= 531) { block = 256; stride = 532; }
+        if (j.max_seg_dlen <= 275)      { block = 256; stride = 276; }
+        else if (j.max_seg_dlen <= 531) { block = 256; stride = 532; }
         else                             { block = 128; stride = 1044; }
-        uint32_t grid = (g->n_segs + block - 1) / block;
+        uint32_t grid = (j.n_segs + block - 1) / block;
         hipLaunchKernelGGL(lz4_decode_lane_kernel, dim3(grid), dim3(block),
                            block * stride + block * 16, g->stream,
-                           g->d_data, g->d_scratch, g->d_segs, g->n_segs, stride,
+                           j.data, j.out, j.segs, j.n_segs, stride,
                            g->d_error);
         HIP_TRY(hipGetLastError());
         return CSTRIPE_OK;
     }
-    uint32_t in_cap = (g->max_seg_comp + 8 + 15) & ~15u;
-    uint32_t out_cap = (g->max_seg_dlen + 15) & ~15u;
+    uint32_t in_cap = (j.max_seg_comp + 8 + 15) & ~15u;
+    uint32_t out_cap = (j.max_seg_dlen + 15) & ~15u;
     if (in_cap + out_cap <= 64 * 1024) {
-        hipLaunchKernelGGL(lz4_decode_lds_kernel, dim3(g->n_segs), dim3(WAVE),
+        hipLaunchKernelGGL(lz4_decode_lds_kernel, dim3(j.n_segs), dim3(WAVE),
                            in_cap + out_cap, g->stream,
-                           g->d_data, g->d_scratch, g->d_segs, in_cap, g->d_error);
+                           j.data, j.out, j.segs, in_cap, g->d_error);
     } else {
-        hipLaunchKernelGGL(lz4_decode_kernel, dim3(g->n_segs), dim3(WAVE), 0, g->stream,
-                           g->d_data, g->d_scratch, g->d_segs, g->d_error);
+        hipLaunchKernelGGL(lz4_decode_kernel, dim3(j.n_segs), dim3(WAVE), 0, g->stream,
+                           j.data, j.out, j.segs, g->d_error);
     }
     /* a failed launch would leave d_scratch stale while later memcpys
        succeed -> silent garbage; surface it as an error (round-1 advisor) */
     HIP_TRY(hipGetLastError());
     return CSTRIPE_OK;
+}
+
+/* the scan's own decode grid: every staged LZ4 / restricted-zstd segment of
+ * the fixed-width columns into d_scratch */
+static int launch_decode(cs_gpu_state *g)
+{
+    DecodeJob j{g->d_data, g->d_scratch, g->d_segs, g->n_segs, g->max_seg_comp,
+                g->max_seg_dlen, g->segs_16aligned, g->d_zsegs, g->n_zsegs,
+                g->max_zseg_comp, g->max_zseg_dlen};
+    return launch_decode_job(g, j);
+}
+
+/* =====================================================================
+ * VARTEXT — variable-length text through a per-scan device dictionary.
+ *
+ * The varlena branch of DeserializeDatumArray (columnar_reader.c:1559-1565:
+ * fetch_att / att_addlength_datum / att_align_nominal, one dependent step
+ * per datum) run once per stage instead of once per row per query. For each
+ * projected VARTEXT column, over the scan's SELECTED chunk groups:
+ *   decode   the chunks' streams into a temporary buffer — the same LZ4 /
+ *            restricted-zstd decode kernels over a SEPARATE segment list, so
+ *            the per-call launch_decode of the query paths never touches
+ *            text; NONE and host-decoded zstd/pglz chunks are staged raw
+ *   walk     vt_walk_kernel: one wave per chunk-column; windows of the
+ *            stream are staged into LDS with coalesced loads, lane 0 walks
+ *            the headers at LDS latency (csvt_step, vartext.h), the wave
+ *            writes (offset, length) words out coalesced. Bounded by the
+ *            chunk's decompressed_size; overrun / miscount raises a flag
+ *   dict     vt_dict_kernel: every value hashes its payload into a global
+ *            open-addressing table; an EMPTY slot is claimed by one
+ *            atomicCAS that stores a reference to the claimer's bytes
+ *            (immutable since the walk), a loser compares bytes and adopts
+ *            the slot or probes on; winners also reserve their place in the
+ *            compact entry list and in the gather buffer
+ *   gather   vt_gather_kernel: entry records + representative strings into
+ *            one buffer, one DtoH copy; the host sorts by memcmp and uploads
+ *            a slot -> rank table
+ *   remap    vt_remap_kernel: int32 ranks into the column's scratch region
+ * After that the column is a dense/sparse I32 column to every query kernel.
+ * ===================================================================== */
+
+#define VT_WIN      8192u   /* stream bytes per LDS window (multiple of 4) */
+#define VT_OUT      1024u   /* values buffered per window */
+#define VT_EMPTY    (~0ull)
+#define VT_ERR_WALK     256
+#define VT_ERR_DISTINCT 512
+
+struct VtChunk {
+    uint64_t raw_off;       /* decoded stream in the temp buffer, 16 B-aligned */
+    uint64_t val_base;      /* index of the chunk's first value in vpos */
+    uint64_t rank_off;      /* into d_scratch: n_present int32 ranks */
+    uint32_t raw_len;       /* decompressed_size — the walk's bound */
+    uint32_t n_present;
+};
+
+/* a value reference: payload offset in the temp buffer << 16 | length
+ * (<= CSTRIPE_VARTEXT_MAX_LEN, checked by csvt_step); never VT_EMPTY */
+struct VtEntry {
+    unsigned long long ref;
+    unsigned long long boff;    /* byte offset of the copy in the gather buffer */
+    uint32_t slot;
+    uint32_t pad;
+};
+
+__global__ __launch_bounds__(WAVE) void vt_walk_kernel(
+    const uint8_t *__restrict__ raw, const VtChunk *__restrict__ chunks,
+    unsigned long long *__restrict__ vpos, int *__restrict__ err)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t win[VT_WIN];
+    __shared__ unsigned long long outb[VT_OUT];
+    __shared__ uint32_t s_n, s_adv, s_bad;
+    const VtChunk ck = chunks[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    const uint64_t len = ck.raw_len;
+    uint64_t pos = 0;               /* always 4-aligned: datums are padded */
+    uint32_t count = 0;
+    bool bad = false;
+    while (pos < len && count < ck.n_present && !bad) {
+        const uint32_t wlen = (uint32_t)min((uint64_t)VT_WIN, len - pos);
+        /* raw_off is 16-aligned and the buffer ends in slack, so whole
+         * dwords load even when wlen is not a multiple of 4 */
+        const uint32_t *src = (const uint32_t *)(raw + ck.raw_off + pos);
+        for (uint32_t i = lane; i < (wlen + 3) / 4; i += WAVE)
+            ((uint32_t *)win)[i] = src[i];
+        __syncthreads();
+        if (lane == 0) {
+            uint32_t w = 0, n = 0, e = 0;
+            /* w < wlen and w 4-aligned: a 4-byte header csvt_step reads
+             * (only when >= 4 stream bytes remain) lies inside the window */
+            while (w < wlen && n < VT_OUT && count + n < ck.n_present) {
+                uint32_t po, pl, adv;
+                if (csvt_step(win + w, len - (pos + w), &po, &pl, &adv)) { e = 1; break; }
+                outb[n++] = ((unsigned long long)(ck.raw_off + pos + w + po) << 16) | pl;
+                w += adv;           /* past wlen when the datum outgrows the
+                                     * window: the next window starts there */
+            }
+            s_n = n; s_adv = w; s_bad = e;
+        }
+        __syncthreads();
+        const uint32_t n = s_n;
+        for (uint32_t i = lane; i < n; i += WAVE)
+            vpos[ck.val_base + count + i] = outb[i];
+        count += n;
+        pos += s_adv;
+        bad = s_bad != 0;
+        __syncthreads();
+    }
+    if (lane == 0 && (bad || count != ck.n_present || pos < len))
+        atomicOr(err, VT_ERR_WALK);
+}
+
+__device__ inline uint64_t vt_hash(const uint8_t *p, uint32_t len)
+{
+    uint64_t h = 0xcbf29ce484222325ull;             /* FNV-1a, then a finalizer */
+    for (uint32_t i = 0; i < len; i++) { h ^= p[i]; h *= 0x100000001b3ull; }
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33;
+    return h;
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void vt_dict_kernel(
+    const uint8_t *__restrict__ raw, const unsigned long long *__restrict__ vpos,
+    uint64_t n_values, unsigned long long *table, uint64_t slots,
+    uint32_t *__restrict__ vslot, VtEntry *__restrict__ entries,
+    unsigned long long *counters, uint32_t max_distinct, int *err)
+{
+    const uint64_t mask = slots - 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < n_values;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const unsigned long long ref = vpos[i];
+        const uint8_t *p = raw + (ref >> 16);
+        const uint32_t len = (uint32_t)(ref & 0xFFFFu);
+        uint64_t slot = vt_hash(p, len) & mask;
+        bool found = false;
+        for (uint64_t probe = 0; probe < slots && !found; probe++) {
+            /* look before claiming: a column of few distinct values would
+             * otherwise send every row's CAS to the same few addresses */
+            unsigned long long cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == VT_EMPTY) {
+                cur = atomicCAS(&table[slot], VT_EMPTY, ref);
+                if (cur == VT_EMPTY) {      /* claimed: this value represents the slot */
+                    const unsigned long long e = atomicAdd(&counters[0], 1ull);
+                    if (e >= max_distinct) {
+                        atomicOr(err, VT_ERR_DISTINCT);
+                    } else {
+                        VtEntry en;
+                        en.ref = ref;
+                        en.boff = atomicAdd(&counters[1], (unsigned long long)len);
+                        en.slot = (uint32_t)slot;
+                        en.pad = 0;
+                        entries[e] = en;
+                    }
+                    found = true;
+                    break;
+                }
+            }
+            /* occupied: the winner's bytes were written by an earlier kernel,
+             * so comparing them needs no flag or fence */
+            if ((uint32_t)(cur & 0xFFFFu) == len) {
+                const uint8_t *q = raw + (cur >> 16);
+                uint32_t k = 0;
+                while (k < len && p[k] == q[k]) k++;
+                if (k == len) { found = true; break; }
+            }
+            slot = (slot + 1) & mask;
+            if ((probe & 63u) == 63u &&
+                (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & VT_ERR_DISTINCT))
+                break;                      /* the stage fails anyway */
+        }
+        if (!found) { atomicOr(err, VT_ERR_DISTINCT); slot = 0; }
+        vslot[i] = (uint32_t)slot;
+    }
+}
+
+/* out = [n_dict VtEntry records][representative strings at boff] */
+__global__ __launch_bounds__(AGG_BLOCK) void vt_gather_kernel(
+    const uint8_t *__restrict__ raw, const VtEntry *__restrict__ entries,
+    uint32_t n_dict, uint8_t *__restrict__ out)
+{
+    uint8_t *obytes = out + (uint64_t)n_dict * sizeof(VtEntry);
+    for (uint32_t e = blockIdx.x * AGG_BLOCK + threadIdx.x; e < n_dict;
+         e += gridDim.x * AGG_BLOCK) {
+        const VtEntry en = entries[e];
+        ((VtEntry *)out)[e] = en;
+        const uint8_t *p = raw + (en.ref >> 16);
+        const uint32_t len = (uint32_t)(en.ref & 0xFFFFu);
+        uint8_t *d = obytes + en.boff;
+        for (uint32_t k = 0; k < len; k++) d[k] = p[k];
+    }
+}
+
+/* one block per chunk-column of the column being remapped */
+__global__ __launch_bounds__(AGG_BLOCK) void vt_remap_kernel(
+    const VtChunk *__restrict__ chunks, const uint32_t *__restrict__ vslot,
+    uint64_t vbeg, const uint32_t *__restrict__ slot2rank, uint8_t *__restrict__ scratch)
+{
+    const VtChunk ck = chunks[blockIdx.x];
+    int32_t *dst = (int32_t *)(scratch + ck.rank_off);
+    const uint32_t *vs = vslot + (ck.val_base - vbeg);
+    for (uint32_t i = threadIdx.x; i < ck.n_present; i += AGG_BLOCK)
+        dst[i] = (int32_t)slot2rank[vs[i]];
+}
+
+/* memcmp order, the shorter string first on a prefix tie */
+static inline int vt_cmp(const uint8_t *a, size_t al, const uint8_t *b, size_t bl)
+{
+    const int c = memcmp(a, b, al < bl ? al : bl);
+    if (c) return c;
+    return al < bl ? -1 : (al > bl ? 1 : 0);
+}
+
+static int vartext_build(cstripe_scan *s, VtTemps &vt)
+{
+    cs_gpu_state *g = s->gpu;
+    cstripe_reader *r = s->r;
+    const uint32_t n_cols = r->head.column_count, n_proj = g->n_proj;
+    s->text_dicts.assign(n_cols, cs_text_dict());
+    std::vector<uint32_t> vcols;
+    for (uint32_t c = 0; c < n_cols; c++)
+        if (g->proj_of_col[c] >= 0 && r->cols[c].type == CSTRIPE_VARTEXT) vcols.push_back(c);
+
+    uint32_t max_distinct = CSTRIPE_VARTEXT_MAX_DISTINCT;
+    if (const char *e = getenv("CSTRIPE_VARTEXT_MAX_DISTINCT")) {
+        const long v = atol(e);
+        if (v >= 1 && (unsigned long)v < max_distinct) max_distinct = (uint32_t)v;
+    }
+
+    /* ---- layout: chunk-columns column-major, their streams and segments ---- */
+    enum { K_RAW, K_LZ4, K_ZR, K_HOST };
+    std::vector<VtChunk> chunks;
+    std::vector<uint8_t> kinds;
+    std::vector<uint64_t> comp_off;
+    std::vector<uint64_t> col_cbeg(vcols.size() + 1, 0), col_vbeg(vcols.size() + 1, 0);
+    uint64_t comp_bytes = 0, raw_bytes = 0, n_values = 0;
+    bool any_host_raw = false;
+    for (size_t ci = 0; ci < vcols.size(); ci++) {
+        const uint32_t c = vcols[ci];
+        col_cbeg[ci] = chunks.size();
+        col_vbeg[ci] = n_values;
+        for (uint32_t gi = 0; gi < g->n_groups; gi++) {
+            const cs_selchunk &sc = s->sel[gi];
+            const cs_skipnode &nd = r->stripes[sc.stripe].nodes[c][sc.chunk];
+            if (nd.n.decompressed_size >= (1ull << 32) || nd.n.n_present > nd.n.row_count) {
+                cs_set_err("VARTEXT column %u: bad chunk sizes in the footer", c);
+                return CSTRIPE_ERR_FORMAT;
+            }
+            uint8_t kind = K_HOST;
+            if (nd.n.comp_type == CSTRIPE_COMP_NONE) kind = K_RAW;
+            else if (nd.n.comp_type == CSTRIPE_COMP_LZ4) kind = K_LZ4;
+            else if (nd.n.comp_type == CSTRIPE_COMP_ZSTD) {
+                kind = K_ZR;
+                for (uint8_t m : nd.seg_modes)
+                    if (m != CSF_SEGMODE_ZR) { kind = K_HOST; break; }
+            } else if (nd.n.comp_type != CSTRIPE_COMP_PGLZ) {
+                cs_set_err("unsupported chunk compression %d", nd.n.comp_type);
+                return CSTRIPE_ERR_FORMAT;
+            }
+            if (kind == K_RAW && nd.n.value_len != nd.n.decompressed_size) {
+                cs_set_err("VARTEXT column %u: uncompressed chunk of %llu bytes claims %llu",
+                           c, (unsigned long long)nd.n.value_len,
+                           (unsigned long long)nd.n.decompressed_size);
+                return CSTRIPE_ERR_FORMAT;
+            }
+            /* the decoders write [decomp_off, +decomp_len) of the chunk's
+             * region: keep every segment inside it */
+            for (const csf_seg &sg : nd.segs)
+                if ((uint64_t)sg.decomp_off + sg.decomp_len > nd.n.decompressed_size ||
+                    (uint64_t)sg.comp_off + sg.comp_len > nd.n.value_len) {
+                    cs_set_err("VARTEXT column %u: segment outside its chunk", c);
+                    return CSTRIPE_ERR_FORMAT;
+                }
+            VtChunk ck{};
+            ck.raw_off = raw_bytes;
+            ck.raw_len = (uint32_t)nd.n.decompressed_size;
+            ck.n_present = nd.n.n_present;
+            ck.val_base = n_values;
+            ck.rank_off = g->colloc_host[(uint64_t)gi * n_proj + g->proj_of_col[c]].val_off;
+            raw_bytes += align_up(nd.n.decompressed_size, 16);
+            n_values += nd.n.n_present;
+            comp_off.push_back(comp_bytes);
+            if (kind == K_LZ4 || kind == K_ZR) comp_bytes += align_up(nd.n.value_len, 16);
+            else any_host_raw = true;
+            chunks.push_back(ck);
+            kinds.push_back(kind);
+        }
+    }
+    col_cbeg[vcols.size()] = chunks.size();
+    col_vbeg[vcols.size()] = n_values;
+    for (size_t ci = 0; ci < vcols.size(); ci++) {
+        s->text_dicts[vcols[ci]].built = true;
+        s->text_dicts[vcols[ci]].offsets.assign(1, 0);
+    }
+
+    if (!chunks.empty()) {
+        /* ---- fill the host staging buffers ---- */
+        std::vector<uint8_t> h_comp(comp_bytes, 0);
+        std::vector<uint8_t> h_raw(any_host_raw ? raw_bytes : 0, 0);
+        std::vector<SegDesc> lsegs, zsegs;
+        DecodeJob job{};
+        job.segs_16aligned = true;
+        size_t k = 0;
+        for (size_t ci = 0; ci < vcols.size(); ci++) {
+            const uint32_t c = vcols[ci];
+            for (uint32_t gi = 0; gi < g->n_groups; gi++, k++) {
+                const cs_selchunk &sc = s->sel[gi];
+                const cs_stripe_info &st = r->stripes[sc.stripe];
+                const cs_skipnode &nd = st.nodes[c][sc.chunk];
+                const uint8_t *src = r->stripe_base(st) + nd.n.value_off;
+                const VtChunk &ck = chunks[k];
+                if (kinds[k] == K_RAW) {
+                    memcpy(h_raw.data() + ck.raw_off, src, nd.n.value_len);
+                } else if (kinds[k] == K_HOST) {
+                    for (const csf_seg &sg : nd.segs) {
+                        uint8_t *dst = h_raw.data() + ck.raw_off + sg.decomp_off;
+                        if (nd.n.comp_type == CSTRIPE_COMP_ZSTD) {
+                            const size_t zr = ZSTD_decompress(dst, sg.decomp_len, src + sg.comp_off, sg.comp_len);
+                            if (ZSTD_isError(zr) || zr != sg.decomp_len) { cs_set_err("zstd host decode failed"); return CSTRIPE_ERR_FORMAT; }
+                        } else {
+                            const uint8_t *pb = src + sg.comp_off;
+                            if (sg.comp_len < CSPGLZ_HDRSZ ||
+                                cspglz_varsize(pb) != sg.comp_len ||
+                                cspglz_rawsize(pb) != (int32_t)sg.decomp_len ||
+                                cspglz_decompress(pb + CSPGLZ_HDRSZ, (int32_t)(sg.comp_len - CSPGLZ_HDRSZ),
+                                                  dst, (int32_t)sg.decomp_len) < 0) {
+                                cs_set_err("pglz host decode failed");
+                                return CSTRIPE_ERR_FORMAT;
+                            }
+                        }
+                    }
+                } else {
+                    memcpy(h_comp.data() + comp_off[k], src, nd.n.value_len);
+                    for (const csf_seg &sg : nd.segs) {
+                        SegDesc sd;
+                        sd.src_off = comp_off[k] + sg.comp_off;
+                        sd.dst_off = ck.raw_off + sg.decomp_off;
+                        sd.comp_len = sg.comp_len;
+                        sd.decomp_len = sg.decomp_len;
+                        if (kinds[k] == K_LZ4) {
+                            job.max_seg_comp = std::max(job.max_seg_comp, sg.comp_len);
+                            job.max_seg_dlen = std::max(job.max_seg_dlen, sg.decomp_len);
+                            if (sg.decomp_off % 16 != 0) job.segs_16aligned = false;
+                            lsegs.push_back(sd);
+                        } else {
+                            job.max_zseg_comp = std::max(job.max_zseg_comp, sg.comp_len);
+                            job.max_zseg_dlen = std::max(job.max_zseg_dlen, sg.decomp_len);
+                            zsegs.push_back(sd);
+                        }
+                    }
+                }
+            }
+        }
+        std::stable_sort(zsegs.begin(), zsegs.end(),
+                         [](const SegDesc &a, const SegDesc &b) { return a.comp_len > b.comp_len; });
+
+        /* ---- device buffers (+256: the decoders' and the walk's whole-word
+         * reads reach a few bytes past a region's end) ---- */
+        uint8_t *t_comp = nullptr, *t_raw = nullptr;
+        VtChunk *d_chunks = nullptr;
+        SegDesc *d_lsegs = nullptr, *d_zs = nullptr;
+        unsigned long long *d_vpos = nullptr;
+        HIP_TRY(vt.alloc(t_comp, comp_bytes + 256));
+        HIP_TRY(vt.alloc(t_raw, raw_bytes + 256));
+        HIP_TRY(vt.alloc(d_chunks, chunks.size() * sizeof(VtChunk)));
+        HIP_TRY(vt.alloc(d_lsegs, lsegs.size() * sizeof(SegDesc)));
+        HIP_TRY(vt.alloc(d_zs, zsegs.size() * sizeof(SegDesc)));
+        HIP_TRY(vt.alloc(d_vpos, n_values * sizeof(unsigned long long)));
+        for (hipEvent_t &e : vt.ev) HIP_TRY(hipEventCreate(&e));
+        if (any_host_raw)
+            HIP_TRY(hipMemcpyAsync(t_raw, h_raw.data(), raw_bytes, hipMemcpyHostToDevice, g->stream));
+        else
+            HIP_TRY(hipMemsetAsync(t_raw + raw_bytes, 0, 256, g->stream));
+        if (comp_bytes)
+            HIP_TRY(hipMemcpyAsync(t_comp, h_comp.data(), comp_bytes, hipMemcpyHostToDevice, g->stream));
+        HIP_TRY(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(VtChunk), hipMemcpyHostToDevice, g->stream));
+        if (!lsegs.empty())
+            HIP_TRY(hipMemcpyAsync(d_lsegs, lsegs.data(), lsegs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, g->stream));
+        if (!zsegs.empty()) {
+            HIP_TRY(hipMemcpyAsync(d_zs, zsegs.data(), zsegs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, g->stream));
+            if (!g->d_zrtab) {      /* no fixed-width column brought the tables */
+                static zr_dtables h_zrtab2;
+                static bool zrtab2_init = false;
+                if (!zrtab2_init) { zr_build_dtables(&h_zrtab2); zrtab2_init = true; }
+                HIP_TRY(hipMalloc(&g->d_zrtab, sizeof(zr_dtables)));
+                HIP_TRY(hipMemcpyAsync(g->d_zrtab, &h_zrtab2, sizeof(h_zrtab2), hipMemcpyHostToDevice, g->stream));
+            }
+        }
+        job.data = t_comp;
+        job.out = t_raw;
+        job.segs = d_lsegs;
+        job.n_segs = (uint32_t)lsegs.size();
+        job.zsegs = d_zs;
+        job.n_zsegs = (uint32_t)zsegs.size();
+
+        /* ---- decode + walk ---- */
+        HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+        HIP_TRY(hipEventRecord(vt.ev[0], g->stream));
+        { int _rc = launch_decode_job(g, job); if (_rc != CSTRIPE_OK) return _rc; }
+        HIP_TRY(hipEventRecord(vt.ev[1], g->stream));
+        hipLaunchKernelGGL(vt_walk_kernel, dim3((uint32_t)chunks.size()), dim3(WAVE), 0, g->stream,
+                           t_raw, d_chunks, d_vpos, g->d_error);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(vt.ev[2], g->stream));
+        int h_err = 0;
+        HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, vt.ev[0], vt.ev[1]);
+        s->last_text_decode_ms = ms;
+        (void)hipEventElapsedTime(&ms, vt.ev[1], vt.ev[2]);
+        s->last_text_walk_ms = ms;
+        if (h_err & ~VT_ERR_WALK) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+        if (h_err & VT_ERR_WALK) {
+            cs_set_err("VARTEXT stream malformed: a datum overruns its chunk or the datum "
+                       "count differs from n_present (device flag %d)", h_err);
+            return CSTRIPE_ERR_FORMAT;
+        }
+
+        /* ---- per column: dictionary, gather, host sort, remap ---- */
+        for (size_t ci = 0; ci < vcols.size(); ci++) {
+            const uint32_t c = vcols[ci];
+            const uint64_t vbeg = col_vbeg[ci], nv = col_vbeg[ci + 1] - vbeg;
+            const uint32_t ncks = (uint32_t)(col_cbeg[ci + 1] - col_cbeg[ci]);
+            if (nv == 0) continue;             /* all NULL: empty dictionary */
+            const uint32_t mark = vt.n_bufs;
+            const uint64_t cap = std::min<uint64_t>(max_distinct, nv);
+            uint64_t slots = 2;
+            while (slots < 2 * cap) slots <<= 1;
+            unsigned long long *d_table = nullptr, *d_cnt = nullptr;
+            uint32_t *d_vslot = nullptr, *d_s2r = nullptr;
+            VtEntry *d_ent = nullptr;
+            uint8_t *d_gather = nullptr;
+            HIP_TRY(vt.alloc(d_table, slots * sizeof(unsigned long long)));
+            HIP_TRY(vt.alloc(d_cnt, 2 * sizeof(unsigned long long)));
+            HIP_TRY(vt.alloc(d_vslot, nv * sizeof(uint32_t)));
+            HIP_TRY(vt.alloc(d_ent, cap * sizeof(VtEntry)));
+            HIP_TRY(hipMemsetAsync(d_table, 0xFF, slots * sizeof(unsigned long long), g->stream));
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), g->stream));
+            const uint64_t vblocks = (nv + AGG_BLOCK - 1) / AGG_BLOCK;
+            const uint32_t dgrid = (uint32_t)std::min<uint64_t>(vblocks, 65536);
+            HIP_TRY(hipEventRecord(vt.ev[3], g->stream));
+            hipLaunchKernelGGL(vt_dict_kernel, dim3(dgrid), dim3(AGG_BLOCK), 0, g->stream,
+                               t_raw, d_vpos + vbeg, nv, d_table, slots, d_vslot, d_ent,
+                               d_cnt, (uint32_t)cap, g->d_error);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(vt.ev[4], g->stream));
+            unsigned long long h_cnt[2] = {0, 0};
+            HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, g->stream));
+            HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+            HIP_TRY(hipStreamSynchronize(g->stream));
+            (void)hipEventElapsedTime(&ms, vt.ev[3], vt.ev[4]);
+            s->last_text_dict_ms += ms;
+            if (h_err & VT_ERR_DISTINCT) {
+                cs_set_err("gpu_stage: VARTEXT column %u holds more than %u distinct values over "
+                           "the selected chunk groups (CSTRIPE_VARTEXT_MAX_DISTINCT) — not "
+                           "pushdownable through the device dictionary", c, max_distinct);
+                return CSTRIPE_ERR_ARG;
+            }
+            const uint32_t n_dict = (uint32_t)h_cnt[0];
+            const uint64_t n_bytes = h_cnt[1];
+            const uint64_t gbytes = (uint64_t)n_dict * sizeof(VtEntry) + n_bytes;
+            HIP_TRY(vt.alloc(d_gather, gbytes));
+            HIP_TRY(hipEventRecord(vt.ev[3], g->stream));
+            hipLaunchKernelGGL(vt_gather_kernel, dim3((n_dict + AGG_BLOCK - 1) / AGG_BLOCK),
+                               dim3(AGG_BLOCK), 0, g->stream, t_raw, d_ent, n_dict, d_gather);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(vt.ev[4], g->stream));
+            std::vector<uint8_t> h_g(gbytes);
+            HIP_TRY(hipMemcpyAsync(h_g.data(), d_gather, gbytes, hipMemcpyDeviceToHost, g->stream));
+            HIP_TRY(hipStreamSynchronize(g->stream));
+            (void)hipEventElapsedTime(&ms, vt.ev[3], vt.ev[4]);
+            s->last_text_dict_ms += ms;
+
+            /* host sort by memcmp; ranks are positions in that order */
+            const VtEntry *ents = (const VtEntry *)h_g.data();
+            const uint8_t *gb = h_g.data() + (uint64_t)n_dict * sizeof(VtEntry);
+            for (uint32_t e = 0; e < n_dict; e++)
+                if (ents[e].boff + (ents[e].ref & 0xFFFFu) > n_bytes || ents[e].slot >= slots) {
+                    cs_set_err("VARTEXT column %u: inconsistent dictionary entry", c);
+                    return CSTRIPE_ERR;
+                }
+            std::vector<uint32_t> order(n_dict);
+            for (uint32_t e = 0; e < n_dict; e++) order[e] = e;
+            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+                return vt_cmp(gb + ents[a].boff, ents[a].ref & 0xFFFFu,
+                              gb + ents[b].boff, ents[b].ref & 0xFFFFu) < 0;
+            });
+            cs_text_dict &d = s->text_dicts[c];
+            d.offsets.assign(1, 0);
+            d.bytes.clear();
+            d.bytes.reserve(n_bytes);
+            std::vector<uint32_t> s2r(slots, 0);
+            for (uint32_t rk = 0; rk < n_dict; rk++) {
+                const VtEntry &en = ents[order[rk]];
+                const uint32_t len = (uint32_t)(en.ref & 0xFFFFu);
+                d.bytes.insert(d.bytes.end(), gb + en.boff, gb + en.boff + len);
+                d.offsets.push_back(d.bytes.size());
+                s2r[en.slot] = rk;
+            }
+            HIP_TRY(vt.alloc(d_s2r, slots * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(d_s2r, s2r.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice, g->stream));
+            HIP_TRY(hipEventRecord(vt.ev[5], g->stream));
+            hipLaunchKernelGGL(vt_remap_kernel, dim3(ncks), dim3(AGG_BLOCK), 0, g->stream,
+                               d_chunks + col_cbeg[ci], d_vslot, vbeg, d_s2r, g->d_scratch);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(vt.ev[6], g->stream));
+            HIP_TRY(hipStreamSynchronize(g->stream));
+            (void)hipEventElapsedTime(&ms, vt.ev[5], vt.ev[6]);
+            s->last_text_remap_ms += ms;
+            vt.free_from(mark);
+        }
+    }
+
+    /* ---- VARTEXT predicates -> integer atoms over ranks (cstripe.h) ---- */
+    for (size_t i = 0; i < s->preds.size(); i++) {
+        const cstripe_pred &q = s->preds[i];
+        if (r->cols[q.column].type != CSTRIPE_VARTEXT) continue;
+        const cs_text_dict &d = s->text_dicts[q.column];
+        const std::string &cst = s->text_consts[(size_t)q.ival];
+        const int64_t n = (int64_t)d.offsets.size() - 1;
+        auto count_below = [&](bool or_equal) -> int64_t {
+            int64_t lo = 0, hi = n;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) / 2;
+                const int cmp = vt_cmp(d.bytes.data() + d.offsets[mid],
+                                       d.offsets[mid + 1] - d.offsets[mid],
+                                       (const uint8_t *)cst.data(), cst.size());
+                if (cmp < 0 || (or_equal && cmp == 0)) lo = mid + 1; else hi = mid;
+            }
+            return lo;
+        };
+        const int64_t lb = count_below(false), ub = count_below(true);
+        uint8_t op = (uint8_t)q.op;
+        int64_t iv = 0;
+        switch (q.op) {
+            case CSTRIPE_PRED_EQ:
+            case CSTRIPE_PRED_NE: iv = lb != ub ? lb : -1; break;   /* -1: absent */
+            case CSTRIPE_PRED_LT: iv = lb; break;
+            case CSTRIPE_PRED_LE: op = CSTRIPE_PRED_LT; iv = ub; break;
+            case CSTRIPE_PRED_GE: op = CSTRIPE_PRED_GT; iv = lb - 1; break;
+            case CSTRIPE_PRED_GT: iv = ub - 1; break;
+            default: cs_set_err("bad predicate op %u", q.op); return CSTRIPE_ERR_ARG;
+        }
+        g->tpred_op[i] = op;
+        g->tpred_ival[i] = iv;
+    }
+    return CSTRIPE_OK;
+}
+
+/* true when the spec reads a VARTEXT column as a value: its ranks are a
+ * per-scan coding, so only COUNT_COL (presence) means anything */
+static bool agg_reads_vartext(const cstripe_reader *r, const cstripe_agg_spec &a)
+{
+    auto vt = [&](int32_t col) {
+        return col >= 0 && col < (int32_t)r->head.column_count &&
+               r->cols[col].type == CSTRIPE_VARTEXT;
+    };
+    switch (a.kind) {
+        case CSTRIPE_AGG_COUNT_STAR:
+        case CSTRIPE_AGG_COUNT_COL:        return false;
+        case CSTRIPE_AGG_SUM_PROD_I64:
+        case CSTRIPE_AGG_SUM_DISC_I64:     return vt(a.col_a) || vt(a.col_b);
+        case CSTRIPE_AGG_SUM_DISC_TAX_I64: return vt(a.col_a) || vt(a.col_b) || vt(a.col_c);
+        default:                           return vt(a.col_a);
+    }
+}
+
+/* the one place a scan's predicates become device PredD atoms (scan_agg and
+ * its grouped form, scan_agg_hashed, scan_select): a VARTEXT predicate goes
+ * in as its stage-time translation over dictionary ranks */
+static void fill_preds(const cstripe_scan *s, AggParams &p)
+{
+    const cs_gpu_state *g = s->gpu;
+    const cstripe_reader *r = s->r;
+    p.n_preds = (uint32_t)s->preds.size();
+    for (uint32_t i = 0; i < p.n_preds; i++) {
+        const cstripe_pred &q = s->preds[i];
+        p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
+        p.preds[i].op = (uint8_t)q.op;
+        uint8_t t = r->cols[q.column].type;
+        p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
+        p.preds[i].gend = (i + 1 == p.n_preds ||
+                           s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
+        p.preds[i].ival = q.ival;
+        p.preds[i].fval = q.fval;
+        if (t == CSTRIPE_VARTEXT) {
+            p.preds[i].op = g->tpred_op[i];
+            p.preds[i].ival = g->tpred_ival[i];
+            p.preds[i].fval = 0.0;
+        }
+    }
 }
 
 /* =====================================================================
@@ -3612,17 +4298,7 @@ int csgpu_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
     p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
     if (p.tiles_per_group == 0) p.tiles_per_group = 1;
     p.n_groups = g->n_groups;
-    for (uint32_t i = 0; i < p.n_preds; i++) {
-        const cstripe_pred &q = s->preds[i];
-        p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
-        p.preds[i].op = (uint8_t)q.op;
-        uint8_t t = r->cols[q.column].type;
-        p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
-        p.preds[i].gend = (i + 1 == p.n_preds ||
-                           s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
-        p.preds[i].ival = q.ival;
-        p.preds[i].fval = q.fval;
-    }
+    fill_preds(s, p);
     auto proj_of = [&](int32_t col) -> int {
         if (col < 0 || col >= (int32_t)r->head.column_count) return -1;
         return g->proj_of_col[col];
@@ -3632,6 +4308,7 @@ int csgpu_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
         p.aggs[i].one = aggs[i].one;
         int pa = proj_of(aggs[i].col_a), pb = proj_of(aggs[i].col_b), pc = proj_of(aggs[i].col_c);
         if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && pa < 0) { cs_set_err("agg %u: col_a not projected", i); return CSTRIPE_ERR_ARG; }
+        if (agg_reads_vartext(r, aggs[i])) { cs_set_err("agg %u: a VARTEXT column can only be the operand of COUNT_COL", i); return CSTRIPE_ERR_ARG; }
         p.aggs[i].proj_a = (uint8_t)(pa < 0 ? 0 : pa);
         p.aggs[i].proj_b = (uint8_t)(pb < 0 ? 0 : pb);
         p.aggs[i].proj_c = (uint8_t)(pc < 0 ? 0 : pc);
@@ -4197,6 +4874,13 @@ int csgpu_fetch_batch(cstripe_scan *s, uint32_t gi, cstripe_batch *batch)
     cs_gpu_state *g = s->gpu;
     cstripe_reader *r = s->r;
     if (gi >= s->sel.size()) return CSTRIPE_END;
+    for (uint32_t c = 0; c < r->head.column_count && batch->col_values; c++)
+        if (batch->col_values[c] && g->proj_of_col[c] >= 0 &&
+            r->cols[c].type == CSTRIPE_VARTEXT) {
+            cs_set_err("next_batch: column %u is VARTEXT — no batch access to variable-length "
+                       "text; pass NULL for it (scan_select returns dictionary ranks)", c);
+            return CSTRIPE_ERR_ARG;
+        }
 
     /* make sure scratch holds decoded data (decode everything once) */
     if ((g->n_segs > 0 || g->n_zsegs > 0) && !g->batch_decoded) {
@@ -4624,17 +5308,7 @@ static int select_prepare(cstripe_scan *s, AggParams &p)
     p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
     if (p.tiles_per_group == 0) p.tiles_per_group = 1;
     p.n_groups = g->n_groups;
-    for (uint32_t i = 0; i < p.n_preds; i++) {
-        const cstripe_pred &q = s->preds[i];
-        p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
-        p.preds[i].op = (uint8_t)q.op;
-        uint8_t t = r->cols[q.column].type;
-        p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
-        p.preds[i].gend = (i + 1 == p.n_preds ||
-                           s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
-        p.preds[i].ival = q.ival;
-        p.preds[i].fval = q.fval;
-    }
+    fill_preds(s, p);
     for (hipEvent_t &e : g->sev)
         if (!e) HIP_TRY(hipEventCreate(&e));
     const uint64_t n_tiles = (uint64_t)g->n_groups * p.tiles_per_group;
@@ -5197,17 +5871,7 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
     p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
     if (p.tiles_per_group == 0) p.tiles_per_group = 1;
     p.n_groups = g->n_groups;
-    for (uint32_t i = 0; i < p.n_preds; i++) {
-        const cstripe_pred &q = s->preds[i];
-        p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
-        p.preds[i].op = (uint8_t)q.op;
-        uint8_t t = r->cols[q.column].type;
-        p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
-        p.preds[i].gend = (i + 1 == p.n_preds ||
-                           s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
-        p.preds[i].ival = q.ival;
-        p.preds[i].fval = q.fval;
-    }
+    fill_preds(s, p);
     auto proj_of = [&](int32_t col) -> int {
         if (col < 0 || col >= (int32_t)r->head.column_count) return -1;
         return g->proj_of_col[col];
@@ -5218,6 +5882,7 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
         p.aggs[i].one = aggs[i].one;
         int pa = proj_of(aggs[i].col_a), pb = proj_of(aggs[i].col_b), pc = proj_of(aggs[i].col_c);
         if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && pa < 0) { cs_set_err("agg %u: col_a not projected", i); return CSTRIPE_ERR_ARG; }
+        if (agg_reads_vartext(r, aggs[i])) { cs_set_err("agg %u: a VARTEXT column can only be the operand of COUNT_COL", i); return CSTRIPE_ERR_ARG; }
         p.aggs[i].proj_a = (uint8_t)(pa < 0 ? 0 : pa);
         p.aggs[i].proj_b = (uint8_t)(pb < 0 ? 0 : pb);
         p.aggs[i].proj_c = (uint8_t)(pc < 0 ? 0 : pc);
@@ -5260,13 +5925,21 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
             case CSTRIPE_I32:  tlo = INT32_MIN; thi = INT32_MAX; break;
             case CSTRIPE_I64:  tlo = INT64_MIN; thi = INT64_MAX; break;
             case CSTRIPE_TEXT: tlo = 0;         thi = (int64_t)UINT32_MAX; break;
+            case CSTRIPE_VARTEXT: {
+                /* the key is the dictionary rank: exactly [0, n_dict - 1]
+                 * (the skip nodes hold prefix keys, not ranks) */
+                const int64_t nd = (int64_t)s->text_dicts[col].offsets.size() - 1;
+                tlo = 0;
+                thi = nd > 0 ? nd - 1 : 0;
+                break;
+            }
             default:
                 cs_set_err("scan_agg_hashed: key col %u must be I8/I16/I32/I64/TEXT", col);
                 return CSTRIPE_ERR_ARG;
         }
         hp.kproj[k] = (uint32_t)pj;
         ktext[k] = t == CSTRIPE_TEXT;
-        set_range(k, col, ktext[k], tlo, thi);
+        set_range(k, col, ktext[k] || t == CSTRIPE_VARTEXT, tlo, thi);
         total_bits += kbits[k];
     }
     if (total_bits > 63) {

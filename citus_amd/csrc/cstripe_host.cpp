@@ -22,6 +22,7 @@
 #include "lz4_enc.h"
 #include "pglz.h"
 #include "zstd_r.h"
+#include "vartext.h"
 
 #include <hip/hip_runtime.h>
 
@@ -104,6 +105,9 @@ struct ColCur {
     bool has_min_max = false;
     int64_t min_i = 0, max_i = 0;         /* physical encoding (f64 via bit pattern) */
     std::vector<uint8_t> raw_pending;     /* finalized raw value streams, pending compress */
+    /* VARTEXT: memcmp-smallest / -largest value of the current chunk; the
+     * skip node stores their prefix keys (vartext.h) */
+    std::string min_s, max_s;
 };
 
 struct PendingChunk {                     /* raw chunk awaiting compression at flush */
@@ -137,6 +141,9 @@ struct cstripe_writer {
 
     /* footer accumulation */
     std::vector<cs_stripe_info> stripes;
+
+    bool vartext_bad = false;             /* a serialized VARTEXT chunk failed
+                                           * its own header walk */
 };
 
 /* typed min/max update over a span of present values */
@@ -296,6 +303,21 @@ static void finalize_chunk(cstripe_writer *w, uint32_t rows_in_chunk)
         pc.node.row_count = rows_in_chunk;
         uint32_t width = type_width(w->cols[c].type);
         pc.node.n_present = (uint32_t)(pc.raw_values.size() / width);
+        if (w->cols[c].type == CSTRIPE_VARTEXT) {
+            uint32_t np = 0;
+            for (uint8_t e : cc.exists) np += e;
+            pc.node.n_present = np;
+            if (cc.has_min_max) {
+                pc.node.min_i = csvt_prefix_key((const uint8_t *)cc.min_s.data(), (uint32_t)cc.min_s.size());
+                pc.node.max_i = csvt_prefix_key((const uint8_t *)cc.max_s.data(), (uint32_t)cc.max_s.size());
+            }
+            /* self-check: the stream just serialized must walk back to
+             * exactly n_present datums (the reader's header walk) */
+            if (csvt_validate(pc.raw_values.data(), pc.raw_values.size(), np) != 0)
+                w->vartext_bad = true;
+            cc.min_s.clear();
+            cc.max_s.clear();
+        }
         pc.node.decompressed_size = pc.raw_values.size();
         w->pending.push_back(std::move(pc));
         cc.values.clear();
@@ -331,6 +353,15 @@ static bool compress_chunk(const cstripe_writer *w, const PendingChunk &pc, Chun
     size_t target = w->opts.lz4_seg_target_bytes ? w->opts.lz4_seg_target_bytes
                                                  : (size_t)w->opts.lz4_seg_target_kb * 1024;
     uint32_t width = type_width(w->cols[pc.col].type);
+    if (w->cols[pc.col].type == CSTRIPE_VARTEXT)
+        width = 1;      /* a byte stream: no canonical parse applies, matches
+                         * at any distance (generic segment paths only) */
+    if (width == 1 && raw.size() >= (1u << 24)) {
+        /* a segment's decomp_len keeps 24 bits (format.h) */
+        cs_set_err("VARTEXT chunk stream of %zu bytes (max 16 MiB - 1): lower "
+                   "chunk_group_row_limit", raw.size());
+        return false;
+    }
 
     if (codec == CSTRIPE_COMP_PGLZ && !raw.empty()) {
         /* reference PG_LZ layout: ColumnarCompressHeader (varlena len +
@@ -498,6 +529,17 @@ static bool compress_chunk(const cstripe_writer *w, const PendingChunk &pc, Chun
                                          * bytes/frame bound waves/CU, and
                                          * 256 B frames double them vs 512 */
     if (per == 0) per = n;
+    if (w->cols[pc.col].type == CSTRIPE_VARTEXT) {
+        /* text is decoded once per stage into a temporary buffer, never by
+         * the fused 256 B lane-region kernels, so it takes the largest
+         * segment the lane-parallel decoders still handle: a 4x longer match
+         * window for strings that repeat across rows */
+        if (per < 1024) per = 1024;
+        if ((n + per - 1) / per > 4096)
+            per = (((n + 4095) / 4096) + 15) / 16 * 16;   /* long strings: stay
+                                                           * under the 4096-
+                                                           * segment cap */
+    }
     /* caps: segment decomp_len carries the mode byte in bits 24-31 (8 MB is
      * comfortably under 2^24), and a restricted-zstd RAW-block fallback is
      * bounded by the 21-bit block size (1 MB) */
@@ -632,6 +674,11 @@ static int flush_stripe(cstripe_writer *w)
     if (done_rows < w->stripe_rows)
         finalize_chunk(w, w->stripe_rows - done_rows);
 
+    if (w->vartext_bad) {
+        cs_set_err("flush: a serialized VARTEXT chunk failed its own header walk");
+        return CSTRIPE_ERR_FORMAT;
+    }
+
     uint32_t n_cols = (uint32_t)w->cols.size();
     uint32_t n_chunks = (uint32_t)w->chunk_rows.size();
 
@@ -731,6 +778,12 @@ extern "C" int cstripe_write_rows_device(cstripe_writer *w, uint64_t n_rows,
     const uint64_t stripe_limit = w->opts.stripe_row_limit;
     std::vector<uint8_t> types(n_cols);
     for (uint32_t c = 0; c < n_cols; c++) types[c] = w->cols[c].type;
+    for (uint32_t c = 0; c < n_cols; c++)
+        if (types[c] == CSTRIPE_VARTEXT) {
+            cs_set_err("write_rows_device: column %u is VARTEXT — variable-length "
+                       "values go through cstripe_write_rows", c);
+            return CSTRIPE_ERR_ARG;
+        }
 
     uint64_t done = 0;
     while (done < n_rows) {
@@ -813,6 +866,37 @@ extern "C" int cstripe_write_rows(cstripe_writer *w, uint64_t n_rows,
     const uint32_t chunk_limit = w->opts.chunk_group_row_limit;
     const uint64_t stripe_limit = w->opts.stripe_row_limit;
 
+    /* VARTEXT values are checked for the whole batch before anything is
+     * appended: payload <= CSTRIPE_VARTEXT_MAX_LEN, no NUL (PG text) */
+    for (uint32_t c = 0; c < n_cols; c++) {
+        if (w->cols[c].type != CSTRIPE_VARTEXT) continue;
+        const cstripe_vartext_in *vt = (const cstripe_vartext_in *)values[c];
+        if (!vt || !vt->offsets || (!vt->bytes && vt->offsets[n_rows] != vt->offsets[0])) {
+            cs_set_err("write_rows: column %u is VARTEXT and needs a cstripe_vartext_in", c);
+            return CSTRIPE_ERR_ARG;
+        }
+        const uint8_t *nl = (nulls && nulls[c]) ? nulls[c] : nullptr;
+        for (uint64_t i = 0; i < n_rows; i++) {
+            if (vt->offsets[i + 1] < vt->offsets[i]) {
+                cs_set_err("write_rows: column %u row %llu: offsets decrease", c, (unsigned long long)i);
+                return CSTRIPE_ERR_ARG;
+            }
+            if (nl && nl[i]) continue;
+            const uint64_t len = vt->offsets[i + 1] - vt->offsets[i];
+            if (len > CSTRIPE_VARTEXT_MAX_LEN) {
+                cs_set_err("write_rows: column %u row %llu: text value of %llu bytes "
+                           "(max %u)", c, (unsigned long long)i,
+                           (unsigned long long)len, CSTRIPE_VARTEXT_MAX_LEN);
+                return CSTRIPE_ERR_ARG;
+            }
+            if (len && memchr(vt->bytes + vt->offsets[i], 0, len)) {
+                cs_set_err("write_rows: column %u row %llu: text value holds a NUL byte",
+                           c, (unsigned long long)i);
+                return CSTRIPE_ERR_ARG;
+            }
+        }
+    }
+
     uint64_t done = 0;
     while (done < n_rows) {
         uint32_t in_chunk = w->stripe_rows % chunk_limit;
@@ -825,6 +909,47 @@ extern "C" int cstripe_write_rows(cstripe_writer *w, uint64_t n_rows,
             uint32_t width = type_width(w->cols[c].type);
             const uint8_t *src = (const uint8_t *)values[c] + done * width;
             const uint8_t *nl = (nulls && nulls[c]) ? nulls[c] + done : nullptr;
+            if (w->cols[c].type == CSTRIPE_VARTEXT) {
+                /* SerializeSingleDatum for a varlena, typalign 'i'
+                 * (columnar_writer.c:555-585): short 1-byte header when the
+                 * whole datum fits 127 bytes, else the 4-byte header; zero
+                 * padding to the next 4-byte boundary */
+                const cstripe_vartext_in *vt = (const cstripe_vartext_in *)values[c];
+                size_t base = cc.exists.size();
+                cc.exists.resize(base + span);
+                for (uint64_t i = 0; i < span; i++) {
+                    if (nl && nl[i]) { cc.exists[base + i] = 0; continue; }
+                    cc.exists[base + i] = 1;
+                    const uint8_t *pv = vt->bytes + vt->offsets[done + i];
+                    const uint32_t len = (uint32_t)(vt->offsets[done + i + 1] - vt->offsets[done + i]);
+                    if (len + 1 <= 127) {
+                        cc.values.push_back((uint8_t)(((len + 1) << 1) | 1u));
+                    } else {
+                        const uint32_t h = (len + 4) << 2;
+                        for (int b = 0; b < 4; b++) cc.values.push_back((uint8_t)(h >> (8 * b)));
+                    }
+                    if (len) cc.values.insert(cc.values.end(), pv, pv + len);
+                    while (cc.values.size() & 3) cc.values.push_back(0);
+                    /* memcmp order, shorter first on a prefix tie */
+                    auto less = [](const uint8_t *a, uint32_t al, const std::string &b) {
+                        const int r = memcmp(a, b.data(), std::min<size_t>(al, b.size()));
+                        return r < 0 || (r == 0 && al < b.size());
+                    };
+                    auto greater = [](const uint8_t *a, uint32_t al, const std::string &b) {
+                        const int r = memcmp(a, b.data(), std::min<size_t>(al, b.size()));
+                        return r > 0 || (r == 0 && al > b.size());
+                    };
+                    if (!cc.has_min_max) {
+                        cc.min_s.assign((const char *)pv, len);
+                        cc.max_s = cc.min_s;
+                        cc.has_min_max = true;
+                    } else {
+                        if (less(pv, len, cc.min_s)) cc.min_s.assign((const char *)pv, len);
+                        if (greater(pv, len, cc.max_s)) cc.max_s.assign((const char *)pv, len);
+                    }
+                }
+                continue;
+            }
             if (w->cols[c].type == CSTRIPE_TEXT) {
                 /* slots must be well-formed short varlena (hdr odd, total
                  * length 2..4 incl. header: payload <= 3 bytes) */
@@ -872,6 +997,20 @@ extern "C" int cstripe_write_rows(cstripe_writer *w, uint64_t n_rows,
         }
     }
     return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_vartext_validate(const uint8_t *stream, uint64_t len, uint32_t n_values)
+{
+    if (!stream && len) { cs_set_err("vartext_validate: null stream"); return CSTRIPE_ERR_ARG; }
+    const int rc = csvt_validate(stream, len, n_values);
+    if (rc == 0) return CSTRIPE_OK;
+    static const char *const why[] = {"", "header form never written (compressed/external varlena)",
+        "datum shorter than its header", "datum overruns the stream",
+        "payload longer than CSTRIPE_VARTEXT_MAX_LEN", "fewer datums than n_values",
+        "more datums than n_values"};
+    cs_set_err("vartext stream (%llu bytes, %u values): %s",
+               (unsigned long long)len, n_values, why[rc]);
+    return CSTRIPE_ERR_FORMAT;
 }
 
 static void footer_append(std::vector<uint8_t> &buf, const void *p, size_t n)
@@ -1093,8 +1232,23 @@ extern "C" int cstripe_column_def(const cstripe_reader *r, uint32_t col, cstripe
  * BuildBaseConstraint/UpdateConstraint/predicate_refuted_by combination of
  * SelectedChunkMask (columnar_reader.c:1132-1187) specialized to the
  * pushdownable family. Returns true if NO row in [min,max] can satisfy. */
-static bool pred_refutes(const cstripe_pred &p, uint8_t type, int64_t min_i, int64_t max_i)
+static bool pred_refutes(const cstripe_pred &p, uint8_t type, int64_t min_i, int64_t max_i,
+                         int64_t text_key)
 {
+    if (type == CSTRIPE_VARTEXT) {
+        /* min/max are prefix keys (vartext.h): monotone under memcmp order
+         * but not injective, so every bound is the weak one — a chunk whose
+         * boundary value shares the constant's 7-byte prefix is kept */
+        const int64_t kc = text_key;
+        switch (p.op) {
+            case CSTRIPE_PRED_LT:
+            case CSTRIPE_PRED_LE: return min_i > kc;
+            case CSTRIPE_PRED_GT:
+            case CSTRIPE_PRED_GE: return max_i < kc;
+            case CSTRIPE_PRED_EQ: return kc < min_i || kc > max_i;
+            default:              return false;
+        }
+    }
     if (type == CSTRIPE_F32 || type == CSTRIPE_F64) {
         double mn, mx;
         memcpy(&mn, &min_i, 8);
@@ -1141,13 +1295,34 @@ static bool pred_refutes(const cstripe_pred &p, uint8_t type, int64_t min_i, int
 extern "C" cstripe_scan *cstripe_scan_begin(cstripe_reader *r, uint64_t cols_mask,
                                             const cstripe_pred *preds, uint32_t n_preds)
 {
+    return cstripe_scan_begin_ex(r, cols_mask, preds, n_preds, nullptr, 0);
+}
+
+extern "C" cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_mask,
+                                               const cstripe_pred *preds, uint32_t n_preds,
+                                               const cstripe_text_const *text_consts,
+                                               uint32_t n_text_consts)
+{
     if (!r) { cs_set_err("scan_begin: null reader"); return nullptr; }
     auto *s = new cstripe_scan();
     s->r = r;
     s->cols_mask = cols_mask;
     if (n_preds > CSTRIPE_MAX_PREDS) { cs_set_err("too many predicates (max %d)", CSTRIPE_MAX_PREDS); delete s; return nullptr; }
+    for (uint32_t i = 0; i < n_text_consts; i++) {
+        if (!text_consts || (!text_consts[i].data && text_consts[i].len)) { cs_set_err("scan_begin: text constant %u has no data", i); delete s; return nullptr; }
+        s->text_consts.emplace_back((const char *)text_consts[i].data, text_consts[i].len);
+    }
     for (uint32_t i = 0; i < n_preds; i++) {
         if (preds[i].column >= r->cols.size()) { cs_set_err("pred column out of range"); delete s; return nullptr; }
+        if (r->cols[preds[i].column].type == CSTRIPE_VARTEXT &&
+            (preds[i].ival < 0 || (uint64_t)preds[i].ival >= n_text_consts)) {
+            cs_set_err("scan_begin: predicate %u on VARTEXT column %u needs a string "
+                       "constant: ival %lld is not an index into the %u text constants "
+                       "(cstripe_scan_begin_ex)", i, preds[i].column,
+                       (long long)preds[i].ival, n_text_consts);
+            delete s;
+            return nullptr;
+        }
         s->preds.push_back(preds[i]);
         /* normalize: every predicate belongs to exactly one OR group;
          * standalone conjuncts each get a private id */
@@ -1175,7 +1350,8 @@ extern "C" cstripe_scan *cstripe_scan_begin(cstripe_reader *r, uint64_t cols_mas
                                   * EQ/NE only; kernel not taught the
                                   * transform) */
         for (const auto &p : s->preds)
-            any_text |= r->cols[p.column].type == CSTRIPE_TEXT;
+            any_text |= r->cols[p.column].type == CSTRIPE_TEXT ||
+                        r->cols[p.column].type == CSTRIPE_VARTEXT;
         std::vector<uint8_t> selmask;
         if (!s->preds.empty() && !any_text && dpv != 0 &&
             (dpv == 1 || total_chunks >= 8192) &&
@@ -1211,8 +1387,13 @@ extern "C" cstripe_scan *cstripe_scan_begin(cstripe_reader *r, uint64_t cols_mas
                     const csf_skipnode &nd = st.nodes[p.column][k].n;
                     /* all-NULL chunks have no min/max and are never refuted
                      * (columnar_reader.c:1160-1166) */
+                    int64_t text_key = 0;
+                    if (r->cols[p.column].type == CSTRIPE_VARTEXT) {
+                        const std::string &tc = s->text_consts[(size_t)p.ival];
+                        text_key = csvt_prefix_key((const uint8_t *)tc.data(), (uint32_t)tc.size());
+                    }
                     if (!nd.has_min_max ||
-                        !pred_refutes(p, r->cols[p.column].type, nd.min_i, nd.max_i))
+                        !pred_refutes(p, r->cols[p.column].type, nd.min_i, nd.max_i, text_key))
                         group_refuted = false;
                     j++;
                 }
@@ -1261,6 +1442,33 @@ extern "C" uint64_t cstripe_gpu_staged_bytes(const cstripe_scan *s)
     return s ? csgpu_staged_bytes(s) : 0;
 }
 
+extern "C" int cstripe_scan_text_dict(const cstripe_scan *s, uint32_t col, uint32_t *n,
+                                      const uint64_t **offsets, const uint8_t **bytes)
+{
+    if (!s || !n || !offsets || !bytes) { cs_set_err("scan_text_dict: bad args"); return CSTRIPE_ERR_ARG; }
+    if (!s->gpu) { cs_set_err("scan not staged — the text dictionary is built by cstripe_gpu_stage"); return CSTRIPE_ERR_NOGPU; }
+    if (col >= s->text_dicts.size() || !s->text_dicts[col].built) {
+        cs_set_err("scan_text_dict: column %u is not a projected VARTEXT column", col);
+        return CSTRIPE_ERR_ARG;
+    }
+    const cs_text_dict &d = s->text_dicts[col];
+    *n = (uint32_t)(d.offsets.size() - 1);
+    *offsets = d.offsets.data();
+    *bytes = d.bytes.data();
+    return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_last_text_ms(const cstripe_scan *s, double *decode_ms,
+                                         double *walk_ms, double *dict_ms, double *remap_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (decode_ms) *decode_ms = s->last_text_decode_ms;
+    if (walk_ms) *walk_ms = s->last_text_walk_ms;
+    if (dict_ms) *dict_ms = s->last_text_dict_ms;
+    if (remap_ms) *remap_ms = s->last_text_remap_ms;
+    return CSTRIPE_OK;
+}
+
 extern "C" int cstripe_scan_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
                                 cstripe_partial *out)
 {
@@ -1289,6 +1497,12 @@ extern "C" int cstripe_read_row(cstripe_scan *s, uint64_t row_number,
         return CSTRIPE_ERR_ARG;
     }
     cstripe_reader *r = s->r;
+    for (uint32_t c = 0; c < r->head.column_count; c++)
+        if (col_values[c] && r->cols[c].type == CSTRIPE_VARTEXT) {
+            cs_set_err("read_row: column %u is VARTEXT — no row access to variable-length "
+                       "text; pass NULL for it (scan_select returns dictionary ranks)", c);
+            return CSTRIPE_ERR_ARG;
+        }
     /* locate the containing selected chunk (scan order = global row order;
      * with no predicates every chunk is selected) */
     if (s->rr_gi < 0 || row_number < s->rr_first ||
@@ -1324,6 +1538,7 @@ extern "C" int cstripe_read_row(cstripe_scan *s, uint64_t row_number,
         std::vector<uint8_t *> np(n_cols, nullptr);
         for (uint32_t c = 0; c < n_cols; c++) {
             if (!(s->cols_mask & (1ull << c))) continue;
+            if (r->cols[c].type == CSTRIPE_VARTEXT) continue;   /* not readable here */
             vp[c] = s->rr_vals[c].data();
             np[c] = s->rr_nulls[c].data();
         }

@@ -11,7 +11,11 @@
  *  - value stream: attlen-sized, att_align_nominal-aligned packed values of
  *    PRESENT rows only (SerializeSingleDatum, columnar_writer.c:555-585;
  *    DeserializeDatumArray, columnar_reader.c:1542-1572); for the fixed-width
- *    types supported here, a dense array of the non-null values.
+ *    types supported here, a dense array of the non-null values. A VARTEXT
+ *    column's stream is the same function's varlena output instead (1- or
+ *    4-byte header, payload, padding to 4; vartext.h); it takes the generic
+ *    segment paths only, 1 KiB segments by default, and its skip nodes hold
+ *    7-byte prefix keys (csvt_prefix_key).
  *  - value stream compression: whole-chunk LZ4/ZSTD (columnar_compression.c:
  *    62-158), except that a chunk MAY be stored as N independently decodable
  *    segments (each its own LZ4/ZSTD block over a slice of the decompressed
@@ -214,6 +218,11 @@ static inline uint32_t csf_type_width(uint8_t t)
         case 5: return 4;          /* F32 */
         case 6: return 8;          /* F64 */
         case 7: return 4;          /* TEXT: short-varlena slot (hdr+<=3B) */
+        case 8: return 4;          /* VARTEXT: the width the ABI and the device
+                                    * see — an int32 dictionary rank. The
+                                    * on-disk stream is variable-length
+                                    * varlena datums (vartext.h), never
+                                    * indexed by this width */
         default: return 0;
     }
 }

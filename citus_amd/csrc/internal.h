@@ -56,10 +56,23 @@ struct cs_selchunk {
 
 struct cs_gpu_state;   /* defined in cstripe_gpu.hip */
 
+/* sorted per-scan dictionary of one VARTEXT column (built at stage) */
+struct cs_text_dict {
+    bool built = false;
+    std::vector<uint64_t> offsets;   /* n + 1 */
+    std::vector<uint8_t> bytes;      /* entries in memcmp order */
+};
+
 struct cstripe_scan {
     cstripe_reader *r = nullptr;
     uint64_t cols_mask = 0;
     std::vector<cstripe_pred> preds;
+    std::vector<std::string> text_consts;   /* VARTEXT preds: ival indexes these */
+    std::vector<cs_text_dict> text_dicts;   /* [column]; built at stage */
+    double last_text_decode_ms = 0.0;       /* stage-time VARTEXT split */
+    double last_text_walk_ms = 0.0;
+    double last_text_dict_ms = 0.0;
+    double last_text_remap_ms = 0.0;
     std::vector<cs_selchunk> sel;     /* surviving chunk groups, scan order */
     int64_t chunk_groups_filtered = 0;
     cs_gpu_state *gpu = nullptr;

@@ -91,7 +91,47 @@ typedef enum cstripe_type {
      * whole slots (ival = the constant's slot); GROUP BY keys are the first
      * payload byte (char(1) semantics). */
     CSTRIPE_TEXT = 7,
+    /* general variable-length text (the varlena branch of
+     * DeserializeDatumArray, columnar_reader.c:1559-1565). The value stream
+     * is byte for byte what the reference writes for a text column
+     * (SerializeSingleDatum, columnar_writer.c:555-585, typalign 'i'),
+     * present values only: a datum whose total length (header + payload) is
+     * <= 127 carries the 1-byte short header (total << 1) | 1, any other the
+     * 4-byte little-endian header total << 2 (total includes those 4 bytes);
+     * each datum is zero-padded to a 4-byte boundary. Payload 0 ..
+     * CSTRIPE_VARTEXT_MAX_LEN bytes, no NUL byte. Chunks compress through
+     * the generic codec paths; no canonical parse applies.
+     *
+     * Skip nodes: has_min_max = 1 when any value is present; min_i / max_i
+     * hold the PREFIX KEY of the memcmp-smallest / -largest value — its
+     * first 7 payload bytes big-endian in bits 55..0, zero-padded: a
+     * non-negative int64, monotone under memcmp order, not injective.
+     *
+     * On the device a VARTEXT column is never read as bytes by the query
+     * kernels: cstripe_gpu_stage builds a per-scan sorted dictionary and the
+     * column reads as dense int32 RANKS in it (see cstripe_scan_begin_ex). */
+    CSTRIPE_VARTEXT = 8,
 } cstripe_type;
+
+#define CSTRIPE_VARTEXT_MAX_LEN      65535u
+/* most distinct values of one VARTEXT column over the selected chunk groups
+ * of one scan; the environment variable CSTRIPE_VARTEXT_MAX_DISTINCT (read
+ * per stage) lowers it */
+#define CSTRIPE_VARTEXT_MAX_DISTINCT (1u << 20)
+
+/* cstripe_write_rows input of one VARTEXT column: values[c] points at one of
+ * these; row i of the batch is bytes[offsets[i] .. offsets[i+1]). A null
+ * row's byte range is ignored. */
+typedef struct cstripe_vartext_in {
+    const uint64_t *offsets;   /* n_rows + 1, non-decreasing */
+    const uint8_t  *bytes;
+} cstripe_vartext_in;
+
+/* a string constant of a VARTEXT predicate (cstripe_scan_begin_ex) */
+typedef struct cstripe_text_const {
+    const uint8_t *data;
+    uint32_t       len;
+} cstripe_text_const;
 
 /* compression codec per column chunk — columnar_compression.c:62-270.
  * Values match the reference's CompressionType enum
@@ -259,16 +299,27 @@ typedef struct cstripe_scan   cstripe_scan;
 cstripe_writer *cstripe_write_begin(const char *path, const cstripe_coldef *cols,
                                     uint32_t n_cols, const cstripe_options *opts);
 /* column-batch append: n_rows rows; values[c] = array of column c's physical
- * type, row-aligned; nulls[c] may be NULL (all present) else bytes 1=null. */
+ * type, row-aligned; nulls[c] may be NULL (all present) else bytes 1=null.
+ * A VARTEXT column's values[c] points at a cstripe_vartext_in instead; a
+ * value longer than CSTRIPE_VARTEXT_MAX_LEN or holding a NUL byte fails the
+ * call with CSTRIPE_ERR_ARG before anything is appended. */
 int cstripe_write_rows(cstripe_writer *w, uint64_t n_rows,
                        const void *const *values, const uint8_t *const *nulls);
+/* CSTRIPE_OK when exactly n_values VARTEXT datums tile stream[0..len): every
+ * datum's header is one of the two forms above, no datum overruns the stream
+ * (only the last datum's alignment padding may be missing), and the walk
+ * ends after n_values datums, not sooner and not later; CSTRIPE_ERR_FORMAT
+ * otherwise. The same header walk runs in the writer's self-check and in the
+ * device walk kernel of cstripe_gpu_stage. Host only, no GPU needed. */
+int cstripe_vartext_validate(const uint8_t *stream, uint64_t len, uint32_t n_values);
 int cstripe_write_end(cstripe_writer *w);     /* flush + footer + close; frees w */
 /* device-side append: values[c] are DEVICE pointers to
  * HBM-resident column arrays (query results / ETL). Full chunks are
  * compressed ON the GPU (canonical parses where the data fits; see
  * format.h) so only compressed bytes cross PCIe; other shapes copy back
  * and take the host compressors. Dense rows only — NULL-bearing batches
- * go through cstripe_write_rows. Requires a visible MI355X. */
+ * go through cstripe_write_rows. Requires a visible MI355X. A schema with
+ * a VARTEXT column returns CSTRIPE_ERR_ARG (checked before the device). */
 int cstripe_write_rows_device(cstripe_writer *w, uint64_t n_rows,
                               const void *const *dev_values);
 void cstripe_write_abort(cstripe_writer *w);
@@ -288,6 +339,56 @@ int cstripe_column_def(const cstripe_reader *r, uint32_t col, cstripe_coldef *ou
  * survive). */
 cstripe_scan *cstripe_scan_begin(cstripe_reader *r, uint64_t cols_mask,
                                  const cstripe_pred *preds, uint32_t n_preds);
+/* scan_begin_ex: scan_begin plus string constants for VARTEXT predicates.
+ * For a predicate on a VARTEXT column, ival is an INDEX into text_consts
+ * (copied; the caller's memory is not kept). An index >= n_text_consts
+ * returns NULL with an error; cstripe_scan_begin fails the same way on any
+ * VARTEXT predicate, having no constant to compare against.
+ *  - Row semantics: all six operators compare by memcmp order, the shorter
+ *    string first on a prefix tie (PG "C" collation); a NULL operand fails
+ *    the atom; OR groups as for every type.
+ *  - Chunk refutation (host side; the device prune kernel is skipped when a
+ *    VARTEXT predicate is present, as for TEXT) works on prefix keys, kc =
+ *    key(constant): LT/LE refute when min_key > kc, GT/GE when max_key < kc,
+ *    EQ when kc < min_key or kc > max_key, NE never. Keys are monotone but
+ *    not injective, so a value sharing its 7-byte prefix with a chunk
+ *    boundary never prunes that chunk. All-NULL chunks (no min/max) survive.
+ *  - Device evaluation: cstripe_gpu_stage builds, per projected VARTEXT
+ *    column, a dictionary of the distinct values of the SELECTED chunk
+ *    groups — decode, header walk, a device open-addressing table claimed by
+ *    atomicCAS, one gather + one DtoH copy, a host memcmp sort — and rewrites
+ *    the column as int32 ranks in that sorted dictionary. Ranks follow
+ *    memcmp order, so each predicate becomes one integer atom over ranks
+ *    (lb = entries < c, ub = entries <= c): EQ rank == rank(c), or == -1
+ *    when c is absent; NE the negation; LT rank < lb; LE rank < ub; GE
+ *    rank > lb - 1; GT rank > ub - 1. Every query kernel then treats the
+ *    column as a dense I32 column.
+ *  - Limits: more than CSTRIPE_VARTEXT_MAX_DISTINCT distinct values (or the
+ *    lower CSTRIPE_VARTEXT_MAX_DISTINCT environment value) makes
+ *    cstripe_gpu_stage return CSTRIPE_ERR_ARG naming the column and the
+ *    limit, and leaves the scan unstaged — a "not pushdownable" domain, like
+ *    an over-wide hash key. A malformed stream (a datum that overruns its
+ *    chunk, or a datum count other than n_present) makes it return
+ *    CSTRIPE_ERR_FORMAT; the walk is bounded by decompressed_size, so this
+ *    is a flag, never an out-of-range read.
+ *  - Ranks are PER SCAN: the dictionary covers the selected chunk groups of
+ *    this scan (all files of a shard directory), and a restage rebuilds it.
+ *    Ranks of two scans are not comparable, so cagg_combine_groups across
+ *    scans with text keys needs a common coding and is not supported.
+ *  - What each surface does with a VARTEXT column: predicate column in
+ *    scan_agg / scan_agg_grouped / scan_agg_hashed / scan_select — works;
+ *    aggregate operand — COUNT_COL only, else CSTRIPE_ERR_ARG; scan_select —
+ *    col_values[c] receives int32 ranks (capacity * 4 bytes; NULL gives 0
+ *    plus a null byte), host or device destination; scan_agg_hashed key —
+ *    allowed, key range [0, n_dict - 1], keys[k][g] is the rank, NULL keys
+ *    last, so groups come out in the strings' memcmp order; scan_agg_grouped
+ *    key — CSTRIPE_ERR_ARG (use the hashed form); next_batch / read_row —
+ *    CSTRIPE_ERR_ARG when that column's destination is non-NULL, the other
+ *    columns work when it is NULL. */
+cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_mask,
+                                    const cstripe_pred *preds, uint32_t n_preds,
+                                    const cstripe_text_const *text_consts,
+                                    uint32_t n_text_consts);
 void cstripe_scan_end(cstripe_scan *s);
 int64_t cstripe_scan_chunk_groups_filtered(const cstripe_scan *s);
 
@@ -298,6 +399,21 @@ int64_t cstripe_scan_chunk_groups_filtered(const cstripe_scan *s);
 int cstripe_gpu_stage(cstripe_scan *s, int device_id);
 /* bytes staged to HBM (compressed value streams + exists bitmaps) */
 uint64_t cstripe_gpu_staged_bytes(const cstripe_scan *s);
+
+/* The sorted dictionary of a projected VARTEXT column of a staged scan:
+ * *n entries in memcmp order, entry i = (*bytes)[(*offsets)[i] ..
+ * (*offsets)[i+1]); rank i everywhere in this scan's results means that
+ * string. The pointers are into scan-owned host memory, valid until
+ * cstripe_scan_end or a restage. CSTRIPE_ERR_NOGPU on an unstaged scan,
+ * CSTRIPE_ERR_ARG when col is not a projected VARTEXT column. */
+int cstripe_scan_text_dict(const cstripe_scan *s, uint32_t col, uint32_t *n,
+                           const uint64_t **offsets, const uint8_t **bytes);
+/* device time (hipEvents, milliseconds) of the last cstripe_gpu_stage's
+ * VARTEXT work, all text columns together: stream decode, header walk,
+ * dictionary build (table insert + gather), rank remap. All 0 when the scan
+ * projects no VARTEXT column. Any out pointer may be NULL. */
+int cstripe_scan_last_text_ms(const cstripe_scan *s, double *decode_ms, double *walk_ms,
+                              double *dict_ms, double *remap_ms);
 
 /* The fused hot path: decode(LZ4) -> filter -> partial aggregate, on device.
  * Writes one partial per agg spec. Re-invocable (re-runs over staged data;
@@ -422,7 +538,9 @@ typedef struct cstripe_hgroups {
  *    4-byte slot zero-extended (TEXT groups by slot here, not by first
  *    payload byte — for char(1) the two are the same). NULL keys form their
  *    own group, like the reference's HashAggregate (grouping treats NULLs
- *    as equal): key_nulls[k][g] = 1, keys[k][g] = 0.
+ *    as equal): key_nulls[k][g] = 1, keys[k][g] = 0. A VARTEXT key column
+ *    packs its dictionary rank over [0, n_dict - 1] (not the skip-node
+ *    range) and returns the rank; cstripe_scan_text_dict decodes it.
  *  - Filter, aggregates, NULL operands, PG NaN order, is_null, COUNT never
  *    null: exactly as cstripe_scan_agg_grouped — the same 11 agg kinds, the
  *    same accumulator-to-partial conversion, int128 sums exact. Chunk groups
@@ -496,7 +614,8 @@ int cagg_combine(const cstripe_agg_spec *aggs, uint32_t n_aggs,
  * (those merge too); NULL keys compare equal. Output is sorted like
  * cstripe_scan_agg_hashed's. More than `capacity` result groups returns
  * CSTRIPE_ERR_ARG with the needed count in out->n_groups and writes nothing
- * else. */
+ * else. VARTEXT keys are per-scan dictionary ranks: parts from different
+ * scans do not share a coding, so merging them here is out of scope. */
 int cagg_combine_groups(const cstripe_agg_spec *aggs, uint32_t n_aggs, uint32_t n_key_cols,
                         const cstripe_hgroups *parts, uint32_t n_parts,
                         cstripe_hgroups *out, uint64_t capacity);
