@@ -619,6 +619,43 @@ def test_tail_segment_fused_parity(tmp_path):
         mask = a < 2400
         assert gp[0].i128 == int((a[mask].astype(object) * b[mask].astype(object)).sum())
 
+    # The default writer now stores this data as canonical P(2), which the
+    # stage code never fuses (any canonical chunk clears `fusable`), so the
+    # loop above covers the canonical readers. The fused kernel itself needs
+    # generic LZ4 (canonical=0) with every chunk group compressed: the
+    # rows % 32 == 1 counts go into ONE chunk, since a trailing 1-row chunk
+    # group is stored raw and a raw chunk clears `fusable` for the whole scan.
+    for n in (10001, 9985):
+        a = ((np.arange(n, dtype=np.int64) * 2654435761) % 5000).astype(np.int64)
+        b = ((np.arange(n, dtype=np.int64) * 40503) % 9000).astype(np.int64)
+        path = str(tmp_path / f"tailfused{n}.cs")
+        ca.write_table(path, [("a", ca.I64, 0), ("b", ca.I64, 0)], [a, b],
+                       compression=ca.COMP_LZ4, canonical=0,
+                       chunk_group_row_limit=n)
+        for col in futil.read_footer(path)["stripes"][0]["nodes"]:
+            assert len(col) == 1
+            assert col[0]["comp_type"] == ca.COMP_LZ4
+            segs = col[0]["segs"]
+            assert [s["mode"] for s in segs] == [futil.SEGMODE_GENERIC] * len(segs)
+            assert [s["decomp_len"] for s in segs[:-1]] == [256] * (len(segs) - 1)
+            assert segs[-1]["decomp_len"] == (n * 8) % 256     # 8 B for 9985
+        preds = [(0, ca.PRED_LT, 2400)]
+        aggs = [(ca.AGG_SUM_PROD_I64, 0, 1), (ca.AGG_COUNT_STAR, -1),
+                (ca.AGG_SUM_I64, 1)]
+        with oracle.OracleTable(path) as t:
+            op, ofilt = t.scan_agg(preds, aggs)
+        with ca.Reader(path) as r, \
+                r.scan(cols_mask=ca.agg_cols_mask(aggs), preds=preds) as s:
+            s.stage()
+            gp = s.agg(aggs)
+            assert s.last_fused, f"n={n}: the fused kernel did not run"
+            assert s.chunk_groups_filtered == ofilt
+        assert_parity(op, gp, aggs)
+        mask = a < 2400
+        assert gp[0].i128 == int((a[mask].astype(object) * b[mask].astype(object)).sum())
+        assert gp[1].count == int(mask.sum())
+        assert gp[2].i128 == int(b[mask].astype(object).sum())
+
 
 def test_nan_semantics_parity(tmp_path):
     """PG float ordering: NaN sorts above every value and equals itself —
