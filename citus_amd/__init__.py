@@ -113,6 +113,16 @@ class Rows(C.Structure):
                 ("row_numbers", C.c_void_p)]
 
 
+MAX_ORDER_COLS = 4
+MAX_TOPN = 1 << 20
+ORDER_DESC = 1
+ORDER_NULLS_FIRST = 2            # absent = NULLS LAST
+
+
+class OrderKey(C.Structure):
+    _fields_ = [("column", C.c_uint32), ("flags", C.c_uint32)]
+
+
 MAX_HASH_KEY_COLS = 4
 MAX_HASH_GROUPS = 1 << 24
 
@@ -216,6 +226,12 @@ _select = _sig("cstripe_scan_select", C.c_int,
 _last_select_ms = _sig("cstripe_scan_last_select_ms", C.c_int,
                        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.POINTER(C.c_double)])
+_select_topn = _sig("cstripe_scan_select_topn", C.c_int,
+                    [C.c_void_p, C.POINTER(OrderKey), C.c_uint32, C.c_uint64,
+                     C.POINTER(Rows), C.c_int])
+_last_topn_ms = _sig("cstripe_scan_last_topn_ms", C.c_int,
+                     [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                      C.POINTER(C.c_double)])
 _scan_agg_hashed = _sig("cstripe_scan_agg_hashed", C.c_int,
                         [C.c_void_p, C.POINTER(AggSpec), C.c_uint32,
                          C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64,
@@ -630,6 +646,122 @@ def combine_groups(aggs, n_key_cols, results, capacity=None):
     return _hgroups_result(bufs, hg.n_groups)
 
 
+def parse_order(order):
+    """[(col, desc, nulls_first)] from a list of col, (col, "asc"|"desc") or
+    (col, dir, "first"|"last"); NULL placement defaults to PG's: ascending
+    puts NULLs last, descending puts them first."""
+    out = []
+    for o in order:
+        o = tuple(o) if isinstance(o, (tuple, list)) else (o,)
+        if not 1 <= len(o) <= 3:
+            raise CStripeError(f"order entry {o!r}: want col, (col, dir) or (col, dir, nulls)")
+        d = str(o[1]).lower() if len(o) > 1 else "asc"
+        if d not in ("asc", "desc"):
+            raise CStripeError(f"order entry {o!r}: direction must be 'asc' or 'desc'")
+        desc = d == "desc"
+        first = desc
+        if len(o) > 2:
+            p = str(o[2]).lower()
+            if p not in ("first", "last"):
+                raise CStripeError(f"order entry {o!r}: nulls must be 'first' or 'last'")
+            first = p == "first"
+        out.append((int(o[0]), desc, first))
+    return out
+
+
+def _order_ranks(v):
+    """dense ascending ranks (ties equal) of one order column under the
+    library's comparison rules: integers signed; floats in PG order (NaN
+    greatest and equal to itself, -0.0 = +0.0); bytes by memcmp"""
+    import numpy as np
+    if v.dtype == object:
+        uniq = {b: i for i, b in enumerate(sorted(set(v.tolist())))}
+        return np.array([uniq[b] for b in v], dtype=np.int64)
+    if v.dtype.kind == "f":
+        f = v.astype(np.float64)
+        u = f.view(np.uint64).copy()
+        u[f == 0] = 0                                   # -0.0 = +0.0
+        u[np.isnan(f)] = 0x7FF0000000000001             # one above +inf
+        neg = (u >> np.uint64(63)).astype(bool)
+        v = np.where(neg, ~u, u | np.uint64(1 << 63))
+    return np.unique(v, return_inverse=True)[1].astype(np.int64).reshape(-1)
+
+
+def merge_topn(results, order, limit, offset=0, text=False):
+    """The coordinator's Sort + Limit over per-shard select_topn() results
+    (host numpy): concatenate, order by the rules of select_topn, break ties
+    by (part index, row number), return rows [offset, offset + limit).
+    The order columns must be among the returned values. A VARTEXT order
+    column (listed in a part's "text_cols", or carrying decoded "text")
+    compares the decoded bytes of results[i]["text"][col] — ranks are per
+    scan — and raises CStripeError when a part has none. Returns {"n_rows",
+    "part" (index into results per row), "row_numbers", "values", "nulls"};
+    text=True adds "text" for the columns every part decoded. The merged
+    "values" of a VARTEXT column stay per-scan ranks."""
+    import numpy as np
+    keys = parse_order(order)
+    if limit < 0 or offset < 0:
+        raise CStripeError("merge_topn: limit and offset must be >= 0")
+    results = list(results)
+    if not results:
+        raise CStripeError("merge_topn: no results")
+    for i, res in enumerate(results):
+        if res.get("row_numbers") is None:
+            raise CStripeError(f"merge_topn: part {i} has no row numbers")
+    tcols = set()
+    for res in results:
+        tcols |= set(res.get("text_cols", ())) | set(res.get("text", {}))
+    n_each = [int(res["n_rows"]) for res in results]
+    part = np.repeat(np.arange(len(results), dtype=np.int64), n_each)
+    rn = np.concatenate([np.asarray(res["row_numbers"], dtype=np.int64)[:n]
+                         for res, n in zip(results, n_each)])
+    cols = list(results[0]["values"])
+
+    def cat(field, c, dtype=None):
+        return np.concatenate([np.asarray(res[field][c], dtype=dtype)[:n]
+                               for res, n in zip(results, n_each)])
+
+    def cat_text(c):
+        for i, res in enumerate(results):
+            if c not in res.get("text", {}):
+                raise CStripeError(
+                    f"merge_topn: column {c} is VARTEXT and part {i} carries no decoded "
+                    "text (select_topn(decode_text=True)); ranks of different scans "
+                    "are not comparable")
+        out = np.empty(len(part), dtype=object)
+        out[:] = [b for res, n in zip(results, n_each)
+                  for b in list(res["text"][c])[:n]]
+        return out
+
+    values = {c: cat("values", c) for c in cols}
+    have_nulls = all(res.get("nulls") for res in results)
+    nulls = {c: cat("nulls", c, np.uint8) for c in cols} if have_nulls else {}
+    # np.lexsort: the LAST key is the most significant
+    sort_keys = [rn, part]
+    for c, desc, first in reversed(keys):
+        if c not in values:
+            raise CStripeError(f"merge_topn: order column {c} is not among the values")
+        isnull = nulls[c].astype(bool) if have_nulls else np.zeros(len(part), bool)
+        v = cat_text(c) if c in tcols else values[c]
+        if v.dtype == object:
+            v = v.copy()
+            v[isnull] = b""
+        rank = _order_ranks(v)
+        if desc:
+            rank = -rank
+        rank[isnull] = 0
+        sort_keys.append(rank)
+        sort_keys.append(np.where(isnull, 0, 1) if first else isnull.astype(np.int64))
+    idx = np.lexsort(sort_keys)[offset:offset + limit]
+    res = {"n_rows": len(idx), "part": part[idx], "row_numbers": rn[idx],
+           "values": {c: values[c][idx] for c in cols},
+           "nulls": {c: nulls[c][idx] for c in nulls}}
+    if text:
+        res["text"] = {c: cat_text(c)[idx] for c in cols
+                       if all(c in r_.get("text", {}) for r_ in results)}
+    return res
+
+
 class Scan:
     def __init__(self, reader, cols_mask, preds):
         self._preds, self._texts, n_texts = make_preds_ex(preds)
@@ -817,6 +949,55 @@ class Scan:
         return {c: (None if nulls[c] else bufs[c][0].item())
                 for c in bufs}
 
+    def _row_destinations(self, cols, types, cap, want_nulls, want_row_numbers,
+                          device):
+        """caller-owned destinations of `cap` rows for select / select_topn:
+        (values, nulls, row_numbers, Rows) — numpy arrays, or torch tensors
+        on the scan's device"""
+        ncols = self._reader.column_count
+        if device:
+            import torch
+            dev = torch.device("cuda", self._device if self._device >= 0
+                               else torch.cuda.current_device())
+            DT = {1: torch.int8, 2: torch.int16, 3: torch.int32,
+                  4: torch.int64, 5: torch.float32, 6: torch.float64,
+                  7: torch.int32, 8: torch.int32}
+
+            def alloc(dt):
+                return torch.empty(cap, dtype=dt, device=dev)
+
+            def ptr(a):
+                return a.data_ptr()
+            null_dt, rn_dt = torch.uint8, torch.int64
+            torch.cuda.synchronize(dev)
+        else:
+            import numpy as np
+            DT = {1: np.int8, 2: np.int16, 3: np.int32, 4: np.int64,
+                  5: np.float32, 6: np.float64, 7: np.uint32, 8: np.int32}
+
+            def alloc(dt):
+                return np.zeros(cap, dtype=dt)
+
+            def ptr(a):
+                return a.ctypes.data_as(C.c_void_p).value
+            null_dt, rn_dt = np.uint8, np.int64
+        vals = {c: alloc(DT[types[c]]) for c in cols}
+        nulls = {c: alloc(null_dt) for c in cols} if want_nulls else {}
+        rn = alloc(rn_dt) if want_row_numbers else None
+        rows = Rows()
+        vp = (C.c_void_p * ncols)()
+        for c, a in vals.items():
+            vp[c] = ptr(a)
+        rows.col_values = vp
+        if want_nulls:
+            np_ = (C.c_void_p * ncols)()
+            for c, a in nulls.items():
+                np_[c] = ptr(a)
+            rows.col_nulls = np_
+        if rn is not None:
+            rows.row_numbers = ptr(rn)
+        return vals, nulls, rn, rows
+
     def select_count(self):
         """Rows select() returns: runs the device predicate pass and keeps
         the pass mask on the scan for a following select()."""
@@ -859,47 +1040,8 @@ class Scan:
         m_ms, o_ms, _ = self.last_select_ms
         d_ms = self.last_decode_ms
         cap = max(n, 1)
-        if device:
-            import torch
-            dev = torch.device("cuda", self._device if self._device >= 0
-                               else torch.cuda.current_device())
-            DT = {1: torch.int8, 2: torch.int16, 3: torch.int32,
-                  4: torch.int64, 5: torch.float32, 6: torch.float64,
-                  7: torch.int32, 8: torch.int32}
-
-            def alloc(dt):
-                return torch.empty(cap, dtype=dt, device=dev)
-
-            def ptr(a):
-                return a.data_ptr()
-            null_dt, rn_dt = torch.uint8, torch.int64
-            torch.cuda.synchronize(dev)
-        else:
-            import numpy as np
-            DT = {1: np.int8, 2: np.int16, 3: np.int32, 4: np.int64,
-                  5: np.float32, 6: np.float64, 7: np.uint32, 8: np.int32}
-
-            def alloc(dt):
-                return np.zeros(cap, dtype=dt)
-
-            def ptr(a):
-                return a.ctypes.data_as(C.c_void_p).value
-            null_dt, rn_dt = np.uint8, np.int64
-        vals = {c: alloc(DT[types[c]]) for c in cols}
-        nulls = {c: alloc(null_dt) for c in cols} if want_nulls else {}
-        rn = alloc(rn_dt) if want_row_numbers else None
-        rows = Rows()
-        vp = (C.c_void_p * ncols)()
-        for c, a in vals.items():
-            vp[c] = ptr(a)
-        rows.col_values = vp
-        if want_nulls:
-            np_ = (C.c_void_p * ncols)()
-            for c, a in nulls.items():
-                np_[c] = ptr(a)
-            rows.col_nulls = np_
-        if rn is not None:
-            rows.row_numbers = ptr(rn)
+        vals, nulls, rn, rows = self._row_destinations(
+            cols, types, cap, want_nulls, want_row_numbers, device)
         _check(_select(self._h, C.byref(rows), cap, 1 if device else 0),
                "scan_select")
         k = rows.n_rows
@@ -916,6 +1058,68 @@ class Scan:
         if decode_text:
             if device or not want_nulls:
                 raise CStripeError("select: decode_text needs host mode and want_nulls")
+            res["text"] = {c: self._decode_ranks(c, res["values"][c], res["nulls"][c])
+                           for c in cols if types[c] == VARTEXT}
+        return res
+
+    @property
+    def last_topn_ms(self):
+        """(key build, selection, emit + permute) device ms of the last
+        select_topn call"""
+        k, s, e = C.c_double(), C.c_double(), C.c_double()
+        _check(_last_topn_ms(self._h, C.byref(k), C.byref(s), C.byref(e)),
+               "scan_last_topn_ms")
+        return k.value, s.value, e.value
+
+    def select_topn(self, order, limit, cols=None, want_nulls=True,
+                    want_row_numbers=True, device=False, decode_text=False):
+        """ORDER BY ... LIMIT over the scan (cstripe_scan_select_topn): the
+        first `limit` passing rows in the given order, found on device by a
+        radix select over packed keys — no full sort, no full materialisation.
+        order: list of col, (col, "asc"|"desc") or (col, dir, "first"|"last");
+        NULL placement defaults to PG's (asc -> last, desc -> first). Rows
+        equal on every order column come out in ascending row number.
+        Returns the dictionary of select() — "n_rows" = min(limit, passing
+        rows), arrays of that length in final order — plus "topn_profile"
+        (device ms per stage) and "text_cols" (the VARTEXT columns among
+        "values", whose int32 ranks are per scan). cols, want_nulls,
+        want_row_numbers, device and decode_text as in select()."""
+        r = self._reader
+        ncols = r.column_count
+        keys = parse_order(order)
+        if cols is None:
+            cols = [c for c in range(ncols) if (self._mask >> c) & 1]
+        cols = list(cols)
+        for c in cols:
+            if not 0 <= c < ncols:
+                raise CStripeError(f"select_topn: column {c} out of range")
+        types = {c: r.column_def(c)[1] for c in cols}
+        # every destination holds `limit` entries; an out-of-range limit is
+        # the library's error, so only the allocation is clamped
+        cap = min(max(int(limit), 1), MAX_TOPN)
+        vals, nulls, rn, rows = self._row_destinations(
+            cols, types, cap, want_nulls, want_row_numbers, device)
+        ok = (OrderKey * max(1, len(keys)))()
+        for i, (c, desc, first) in enumerate(keys):
+            ok[i].column = c
+            ok[i].flags = (ORDER_DESC if desc else 0) | \
+                          (ORDER_NULLS_FIRST if first else 0)
+        _check(_select_topn(self._h, ok, len(keys), int(limit), C.byref(rows),
+                            1 if device else 0), "scan_select_topn")
+        k = rows.n_rows
+        key_ms, sel_ms, emit_ms = self.last_topn_ms
+        self.topn_profile = {"decode_ms": self.last_decode_ms, "key_ms": key_ms,
+                             "select_ms": sel_ms, "emit_ms": emit_ms,
+                             "total_ms": self.last_kernel_ms}
+        res = {"n_rows": k,
+               "row_numbers": None if rn is None else rn[:k],
+               "values": {c: a[:k] for c, a in vals.items()},
+               "nulls": {c: a[:k] for c, a in nulls.items()},
+               "text_cols": [c for c in cols if types[c] == VARTEXT],
+               "topn_profile": dict(self.topn_profile)}
+        if decode_text:
+            if device or not want_nulls:
+                raise CStripeError("select_topn: decode_text needs host mode and want_nulls")
             res["text"] = {c: self._decode_ranks(c, res["values"][c], res["nulls"][c])
                            for c in cols if types[c] == VARTEXT}
         return res

@@ -160,6 +160,26 @@ struct cs_gpu_state {
     unsigned long long *d_hcount = nullptr;    /* one word: occupied slots */
     uint64_t hkeys_slots = 0, hcells_n = 0, hokeys_n = 0, hocells_n = 0;
     hipEvent_t hev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    /* scan_select_topn: the compact key array (8 B per passing row), the
+     * radix-select state block, and the refined mask / counts / bases — its
+     * own buffers, the d_sel_* cache above is only ever read. Grow-only. */
+    uint64_t *d_tn_keys = nullptr;      /* [n_pass] packed keys, scan order */
+    uint64_t *d_tn_okeys = nullptr;     /* [limit] keys of the emitted rows */
+    struct TopnState *d_tn_state = nullptr;
+    uint64_t *d_tn_mask = nullptr;      /* [tiles][64] key < T, then final */
+    uint64_t *d_tn_eq = nullptr;        /* [tiles][64] key == T */
+    uint32_t *d_tn_counts = nullptr;    /* [tiles] tie counts, then final */
+    uint64_t *d_tn_tbases = nullptr;    /* [tiles] exclusive scan of ties */
+    uint64_t *d_tn_bases = nullptr;     /* [tiles] exclusive scan of final */
+    uint64_t *d_tn_total = nullptr;     /* [2] ties on T, rows emitted */
+    uint8_t *d_tn_emit = nullptr;       /* scan-order rows before the permute */
+    uint8_t *d_tn_out = nullptr;        /* host-mode permuted staging */
+    uint32_t *d_tn_perm = nullptr;      /* [limit] final order -> scan order */
+    uint64_t tn_keys_n = 0, tn_okeys_n = 0, tn_mask_n = 0, tn_eq_n = 0,
+             tn_counts_n = 0, tn_tbases_n = 0, tn_bases_n = 0,
+             tn_emit_bytes = 0, tn_out_bytes = 0, tn_perm_n = 0;
+    hipEvent_t tev[8] = {nullptr, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, nullptr};
 
     uint64_t data_bytes = 0;
     uint64_t scratch_bytes = 0;
@@ -3067,6 +3087,19 @@ void csgpu_release(cstripe_scan *s)
     if (g->d_hokeys) HIP_DROP(hipFree(g->d_hokeys));
     if (g->d_hocells) HIP_DROP(hipFree(g->d_hocells));
     if (g->d_hcount) HIP_DROP(hipFree(g->d_hcount));
+    if (g->d_tn_keys) HIP_DROP(hipFree(g->d_tn_keys));
+    if (g->d_tn_okeys) HIP_DROP(hipFree(g->d_tn_okeys));
+    if (g->d_tn_state) HIP_DROP(hipFree(g->d_tn_state));
+    if (g->d_tn_mask) HIP_DROP(hipFree(g->d_tn_mask));
+    if (g->d_tn_eq) HIP_DROP(hipFree(g->d_tn_eq));
+    if (g->d_tn_counts) HIP_DROP(hipFree(g->d_tn_counts));
+    if (g->d_tn_tbases) HIP_DROP(hipFree(g->d_tn_tbases));
+    if (g->d_tn_bases) HIP_DROP(hipFree(g->d_tn_bases));
+    if (g->d_tn_total) HIP_DROP(hipFree(g->d_tn_total));
+    if (g->d_tn_emit) HIP_DROP(hipFree(g->d_tn_emit));
+    if (g->d_tn_out) HIP_DROP(hipFree(g->d_tn_out));
+    if (g->d_tn_perm) HIP_DROP(hipFree(g->d_tn_perm));
+    for (hipEvent_t e : g->tev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->hev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->sev) if (e) HIP_DROP(hipEventDestroy(e));
     if (g->ev0) HIP_DROP(hipEventDestroy(g->ev0));
@@ -6150,6 +6183,707 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
         }
     }
     out->n_groups = n;
+    return CSTRIPE_OK;
+}
+
+/* =====================================================================
+ * scan_select_topn — device ORDER BY ... LIMIT over the scan: what the
+ * reference pushes to every worker (WorkerSortClauseList / WorkerLimitCount,
+ * multi_logical_optimizer.c:5038-5212: each shard runs ORDER BY ... LIMIT
+ * limit+offset, the coordinator re-sorts the few rows it gets back).
+ *
+ * The pass mask, tile counts and bases of scan_select are reused READ-ONLY;
+ * everything refined lives in the d_tn_* buffers. On the scan's stream:
+ *
+ *   topn_key_kernel      one block per chunk group x TILE_ROWS tile (the
+ *                        select grid). Each passing row's order tuple packs
+ *                        into ONE 64-bit word whose unsigned order is the
+ *                        requested order, stored at bases[tile] + rank in
+ *                        tile — scan order, select_emit_kernel's arithmetic.
+ *   radix select         MSB first, 8 bits per round, ceil(bits/8) rounds:
+ *     topn_hist_kernel   capped grid, grid-stride over the key array; a
+ *                        256-bin LDS histogram of the round's digit over the
+ *                        keys whose higher digits equal the prefix so far,
+ *                        nonzero bins flushed with one global atomicAdd each
+ *     topn_pick_kernel   one wave: scans the 256 bins, finds the bin where
+ *                        the running count crosses the remaining k, extends
+ *                        the prefix, lowers k, clears the bins
+ *                        After the last round prefix = T, the exact key of
+ *                        the limit-th smallest row, and k = ties on T needed.
+ *   topn_refine_kernel   per tile: key < T words, key == T words, tie count
+ *   select_offsets_kernel  over the tie counts
+ *   topn_final_kernel    per tile: lt | (eq & tie ordinal < ties needed),
+ *                        final counts; ties are taken by scan-order prefix,
+ *                        which is the ascending-row-number tie-break
+ *   select_offsets_kernel  over the final counts
+ *   select_emit_kernel   unchanged, over the refined mask and bases: exactly
+ *                        `limit` rows in scan order
+ *   topn_keygather_kernel  their keys alongside
+ *   (host)               one DtoH copy of `limit` keys, a stable sort
+ *   topn_permute_kernel  values / null bytes / row numbers into final order
+ *
+ * No flag, fence, spin-wait or cross-block dependency exists inside a
+ * kernel; the stages are ordered by kernel boundaries on the stream. The
+ * only global words several blocks touch are the 256 histogram bins, updated
+ * by integer atomicAdd alone, so nothing depends on arrival order. Every
+ * loop is bounded by the key count, the tile size or a constant.
+ * ===================================================================== */
+
+#define TOPN_GRID       2048
+#define TOPN_ERR_RANGE  1024            /* key outside its skip-node range */
+#define TOPN_SIGN       0x8000000000000000ull
+#define TOPN_F_DESC     1u
+#define TOPN_F_NFIRST   2u
+#define TOPN_F_FLOAT    4u
+
+struct TopnParams {
+    uint32_t n_order, tiles_per_group;
+    uint32_t kproj[CSTRIPE_MAX_ORDER_COLS];
+    uint32_t kshift[CSTRIPE_MAX_ORDER_COLS];
+    uint32_t kflags[CSTRIPE_MAX_ORDER_COLS];
+    uint64_t klo[CSTRIPE_MAX_ORDER_COLS];     /* ord(lo) */
+    uint64_t kspan[CSTRIPE_MAX_ORDER_COLS];   /* ord(hi) - ord(lo) */
+    uint64_t n_keys;
+};
+
+struct TopnState {
+    unsigned long long prefix;          /* digits found so far; T at the end */
+    unsigned long long k;               /* rank still wanted inside the prefix */
+    unsigned long long hist[256];
+};
+
+/* order-preserving map of an f64 to u64 under PG float order: every NaN is
+ * one code above +inf, -0.0 is +0.0 (float8_cmp_internal) */
+__host__ __device__ inline uint64_t topn_f64_ord(double v)
+{
+    if (v != v) return 0xFFF0000000000001ull;
+    uint64_t u;
+    __builtin_memcpy(&u, &v, 8);
+    if (u == TOPN_SIGN) u = 0;
+    return (u >> 63) ? ~u : (u | TOPN_SIGN);
+}
+
+/* mask words of one tile into LDS plus the passing rows in earlier slices
+ * (wave `wid` does it; SEL_SLICES == WAVE, one lane per word) */
+__device__ inline void topn_load_words(const uint64_t *__restrict__ mask,
+                                       uint64_t *s_word, uint32_t *s_pre, uint32_t lane)
+{
+    const uint64_t w = mask[(uint64_t)blockIdx.x * SEL_SLICES + lane];
+    const uint32_t pc = (uint32_t)__popcll(w);
+    uint32_t inc = pc;
+    #pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, WAVE);
+        if ((int)lane >= d) inc += t;
+    }
+    s_word[lane] = w;
+    s_pre[lane] = inc - pc;
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void topn_key_kernel(
+    const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
+    const uint32_t *__restrict__ rank, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, const uint64_t *__restrict__ mask,
+    const uint64_t *__restrict__ bases, uint64_t *__restrict__ keys,
+    int *err, const TopnParams tp)
+{
+    __shared__ uint64_t s_word[SEL_SLICES];
+    __shared__ uint32_t s_pre[SEL_SLICES];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    if (wid == 0) topn_load_words(mask, s_word, s_pre, lane);
+    __syncthreads();
+
+    const uint32_t gid = blockIdx.x / tp.tiles_per_group;
+    const uint32_t tile = blockIdx.x % tp.tiles_per_group;
+    const ColLoc *cols = colloc + groups[gid].colbase;
+    const uint64_t tile_base = bases[blockIdx.x];
+
+    for (uint32_t sl = wid; sl < SEL_SLICES; sl += AGG_BLOCK / WAVE) {
+        const uint64_t word = s_word[sl];
+        const uint64_t bit = 1ull << lane;
+        if (!(word & bit)) continue;
+        const uint32_t row = tile * TILE_ROWS + sl * WAVE + lane;
+        const uint64_t idx = tile_base + s_pre[sl] +
+                             (uint32_t)__popcll(word & (bit - 1));
+        /* per column: d = ord(v) - ord(lo) in [0, span], reversed for DESC;
+         * NULL takes the code below (NULLS FIRST) or above all values */
+        uint64_t key = 0;
+        bool in_range = true;
+        for (uint32_t kc = 0; kc < tp.n_order; kc++) {
+            const uint32_t fl = tp.kflags[kc];
+            int64_t kv; double kf;
+            uint64_t code;
+            if (col_value(data, scratch, rank, cols[tp.kproj[kc]], row, kv, kf)) {
+                const uint64_t o = (fl & TOPN_F_FLOAT) ? topn_f64_ord(kf)
+                                                       : ((uint64_t)kv ^ TOPN_SIGN);
+                uint64_t d = o - tp.klo[kc];
+                if (d > tp.kspan[kc]) { in_range = false; d = 0; }
+                if (fl & TOPN_F_DESC) d = tp.kspan[kc] - d;
+                code = (fl & TOPN_F_NFIRST) ? d + 1 : d;
+            } else {
+                code = (fl & TOPN_F_NFIRST) ? 0 : tp.kspan[kc] + 1;
+            }
+            key |= code << tp.kshift[kc];
+        }
+        if (!in_range) atomicOr(err, TOPN_ERR_RANGE);   /* skip nodes lie */
+        if (idx < tp.n_keys) keys[idx] = key;
+    }
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void topn_init_kernel(TopnState *st, uint64_t k)
+{
+    st->hist[threadIdx.x] = 0;          /* AGG_BLOCK == 256 bins */
+    if (threadIdx.x == 0) { st->prefix = 0; st->k = k; }
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void topn_hist_kernel(
+    const uint64_t *__restrict__ keys, uint64_t n, TopnState *st, uint32_t shift)
+{
+    __shared__ uint32_t lh[256];
+    lh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t prefix = st->prefix;
+    const bool top = shift + 8 >= 64;           /* no higher digits */
+    const uint32_t hs = top ? 0 : shift + 8;
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const uint64_t key = keys[i];
+        if (top || (key >> hs) == prefix)
+            atomicAdd(&lh[(key >> shift) & 0xFFu], 1u);
+    }
+    __syncthreads();
+    const uint32_t c = lh[threadIdx.x];
+    if (c) atomicAdd(&st->hist[threadIdx.x], (unsigned long long)c);
+}
+
+__global__ __launch_bounds__(WAVE) void topn_pick_kernel(TopnState *st)
+{
+    const uint32_t lane = threadIdx.x;
+    unsigned long long c[4], sum = 0;
+    #pragma unroll
+    for (uint32_t j = 0; j < 4; j++) { c[j] = st->hist[lane * 4 + j]; sum += c[j]; }
+    const unsigned long long k = st->k;
+    const unsigned long long prefix = st->prefix;
+    unsigned long long inc = sum;
+    #pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const unsigned long long t = (unsigned long long)__shfl_up((long long)inc, d, WAVE);
+        if ((int)lane >= d) inc += t;
+    }
+    unsigned long long run = inc - sum;
+    #pragma unroll
+    for (uint32_t j = 0; j < 4; j++) st->hist[lane * 4 + j] = 0;
+    if (run < k && k <= inc) {          /* exactly one lane: the crossing */
+        #pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            if (k <= run + c[j]) {
+                st->prefix = (prefix << 8) | (lane * 4 + j);
+                st->k = k - run;
+                break;
+            }
+            run += c[j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void topn_refine_kernel(
+    const uint64_t *__restrict__ mask, const uint64_t *__restrict__ bases,
+    const uint64_t *__restrict__ keys, uint64_t n_keys,
+    const TopnState *__restrict__ st, uint64_t *__restrict__ lt_mask,
+    uint64_t *__restrict__ eq_mask, uint32_t *__restrict__ tie_counts)
+{
+    __shared__ uint64_t s_word[SEL_SLICES];
+    __shared__ uint32_t s_pre[SEL_SLICES];
+    __shared__ uint32_t s_cnt[AGG_BLOCK / WAVE];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    if (wid == 0) topn_load_words(mask, s_word, s_pre, lane);
+    __syncthreads();
+    const uint64_t T = st->prefix;
+    const uint64_t tile_base = bases[blockIdx.x];
+    uint32_t wcount = 0;
+    for (uint32_t sl = wid; sl < SEL_SLICES; sl += AGG_BLOCK / WAVE) {
+        const uint64_t word = s_word[sl];
+        const uint64_t bit = 1ull << lane;
+        bool lt = false, eq = false;
+        if (word & bit) {
+            const uint64_t idx = tile_base + s_pre[sl] +
+                                 (uint32_t)__popcll(word & (bit - 1));
+            if (idx < n_keys) {
+                const uint64_t key = keys[idx];
+                lt = key < T;
+                eq = key == T;
+            }
+        }
+        const uint64_t ltw = __ballot(lt), eqw = __ballot(eq);
+        if (lane == 0) {
+            lt_mask[(uint64_t)blockIdx.x * SEL_SLICES + sl] = ltw;
+            eq_mask[(uint64_t)blockIdx.x * SEL_SLICES + sl] = eqw;
+        }
+        wcount += (uint32_t)__popcll(eqw);
+    }
+    if (lane == 0) s_cnt[wid] = wcount;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t w = 0; w < AGG_BLOCK / WAVE; w++) c += s_cnt[w];
+        tie_counts[blockIdx.x] = c;
+    }
+}
+
+/* fin_mask holds the key < T words on entry and the final words on exit:
+ * each word is read and rewritten by the one wave that owns its slice */
+__global__ __launch_bounds__(AGG_BLOCK) void topn_final_kernel(
+    const uint64_t *__restrict__ eq_mask, const uint64_t *__restrict__ tie_bases,
+    const TopnState *__restrict__ st, uint64_t *fin_mask,
+    uint32_t *__restrict__ counts)
+{
+    __shared__ uint64_t s_word[SEL_SLICES];
+    __shared__ uint32_t s_pre[SEL_SLICES];
+    __shared__ uint32_t s_cnt[AGG_BLOCK / WAVE];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    if (wid == 0) topn_load_words(eq_mask, s_word, s_pre, lane);
+    __syncthreads();
+    const uint64_t need = st->k;
+    const uint64_t tie_base = tie_bases[blockIdx.x];
+    uint32_t wcount = 0;
+    for (uint32_t sl = wid; sl < SEL_SLICES; sl += AGG_BLOCK / WAVE) {
+        const uint64_t eqw = s_word[sl];
+        const uint64_t bit = 1ull << lane;
+        const uint64_t ordinal = tie_base + s_pre[sl] +
+                                 (uint32_t)__popcll(eqw & (bit - 1));
+        const bool take = (eqw & bit) && ordinal < need;
+        const uint64_t ltw = fin_mask[(uint64_t)blockIdx.x * SEL_SLICES + sl];
+        const uint64_t fin = ltw | __ballot(take);
+        if (lane == 0) fin_mask[(uint64_t)blockIdx.x * SEL_SLICES + sl] = fin;
+        wcount += (uint32_t)__popcll(fin);
+    }
+    if (lane == 0) s_cnt[wid] = wcount;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (uint32_t w = 0; w < AGG_BLOCK / WAVE; w++) c += s_cnt[w];
+        counts[blockIdx.x] = c;
+    }
+}
+
+/* keys of the rows the final mask keeps, at their emit position */
+__global__ __launch_bounds__(AGG_BLOCK) void topn_keygather_kernel(
+    const uint64_t *__restrict__ mask, const uint64_t *__restrict__ bases,
+    const uint64_t *__restrict__ fin_mask, const uint64_t *__restrict__ fin_bases,
+    const uint64_t *__restrict__ keys, uint64_t n_keys,
+    uint64_t *__restrict__ okeys, uint64_t n_out)
+{
+    __shared__ uint64_t s_word[SEL_SLICES], s_fword[SEL_SLICES];
+    __shared__ uint32_t s_pre[SEL_SLICES], s_fpre[SEL_SLICES];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    if (wid == 0) topn_load_words(mask, s_word, s_pre, lane);
+    if (wid == 1) topn_load_words(fin_mask, s_fword, s_fpre, lane);
+    __syncthreads();
+    const uint64_t tile_base = bases[blockIdx.x];
+    const uint64_t fin_base = fin_bases[blockIdx.x];
+    for (uint32_t sl = wid; sl < SEL_SLICES; sl += AGG_BLOCK / WAVE) {
+        const uint64_t fw = s_fword[sl];
+        const uint64_t bit = 1ull << lane;
+        if (!(fw & bit)) continue;
+        const uint64_t src = tile_base + s_pre[sl] +
+                             (uint32_t)__popcll(s_word[sl] & (bit - 1));
+        const uint64_t dst = fin_base + s_fpre[sl] +
+                             (uint32_t)__popcll(fw & (bit - 1));
+        if (src < n_keys && dst < n_out) okeys[dst] = keys[src];
+    }
+}
+
+struct PermCol {
+    const uint8_t *src_vals;
+    uint8_t *dst_vals;
+    const uint8_t *src_nulls;   /* or nullptr */
+    uint8_t *dst_nulls;
+    uint32_t width;
+    uint32_t pad;
+};
+
+struct PermParams {
+    uint32_t n_cols, pad;
+    uint64_t n;
+    const uint64_t *src_rn;     /* or nullptr */
+    uint64_t *dst_rn;
+    PermCol cols[MAX_PROJ];
+};
+
+__global__ __launch_bounds__(AGG_BLOCK) void topn_permute_kernel(
+    const uint32_t *__restrict__ perm, const PermParams pp)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < pp.n;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const uint64_t src = perm[i];
+        if (src >= pp.n) continue;
+        if (pp.src_rn) pp.dst_rn[i] = pp.src_rn[src];
+        for (uint32_t c = 0; c < pp.n_cols; c++) {
+            const PermCol &pc = pp.cols[c];
+            switch (pc.width) {
+                case 1: pc.dst_vals[i] = pc.src_vals[src]; break;
+                case 2: ((uint16_t *)pc.dst_vals)[i] = ((const uint16_t *)pc.src_vals)[src]; break;
+                case 4: ((uint32_t *)pc.dst_vals)[i] = ((const uint32_t *)pc.src_vals)[src]; break;
+                default: ((uint64_t *)pc.dst_vals)[i] = ((const uint64_t *)pc.src_vals)[src]; break;
+            }
+            if (pc.src_nulls) pc.dst_nulls[i] = pc.src_nulls[src];
+        }
+    }
+}
+
+static void topn_zero_timing(cstripe_scan *s)
+{
+    select_zero_timing(s);
+    s->last_topn_key_ms = s->last_topn_select_ms = s->last_topn_emit_ms = 0;
+}
+
+int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t n_order,
+                      uint64_t limit, cstripe_rows *out, int dst_on_device)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    cs_gpu_state *g = s->gpu;
+    cstripe_reader *r = s->r;
+    const uint32_t n_cols = r->head.column_count;
+    if (!order || !out) { cs_set_err("scan_select_topn: bad args"); return CSTRIPE_ERR_ARG; }
+    if (limit == 0 || limit > CSTRIPE_MAX_TOPN) {
+        cs_set_err("scan_select_topn: limit %llu outside 1..%u",
+                   (unsigned long long)limit, CSTRIPE_MAX_TOPN);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (n_order == 0 || n_order > CSTRIPE_MAX_ORDER_COLS) {
+        cs_set_err("scan_select_topn: %u order columns (1..%d)", n_order, CSTRIPE_MAX_ORDER_COLS);
+        return CSTRIPE_ERR_ARG;
+    }
+
+    TopnParams tp{};
+    tp.n_order = n_order;
+    uint8_t otype[CSTRIPE_MAX_ORDER_COLS] = {0};
+    for (uint32_t k = 0; k < n_order; k++) {
+        const uint32_t col = order[k].column;
+        if (col >= n_cols || g->proj_of_col[col] < 0) {
+            cs_set_err("scan_select_topn: order col %u not projected", col);
+            return CSTRIPE_ERR_ARG;
+        }
+        for (uint32_t j = 0; j < k; j++)
+            if (order[j].column == col) {
+                cs_set_err("scan_select_topn: order col %u repeated", col);
+                return CSTRIPE_ERR_ARG;
+            }
+        if (order[k].flags & ~(CSTRIPE_ORDER_DESC | CSTRIPE_ORDER_NULLS_FIRST)) {
+            cs_set_err("scan_select_topn: order col %u: unknown flags 0x%x", col, order[k].flags);
+            return CSTRIPE_ERR_ARG;
+        }
+        const uint8_t t = r->cols[col].type;
+        if (t == CSTRIPE_TEXT) {
+            cs_set_err("scan_select_topn: order col %u is TEXT — its row-level order in this "
+                       "ABI is whole-slot, not collation; order by a VARTEXT column instead", col);
+            return CSTRIPE_ERR_ARG;
+        }
+        if (t < CSTRIPE_I8 || t > CSTRIPE_VARTEXT) {
+            cs_set_err("scan_select_topn: order col %u must be I8/I16/I32/I64/F32/F64/VARTEXT", col);
+            return CSTRIPE_ERR_ARG;
+        }
+        otype[k] = t;
+        tp.kproj[k] = (uint32_t)g->proj_of_col[col];
+        tp.kflags[k] = ((order[k].flags & CSTRIPE_ORDER_DESC) ? TOPN_F_DESC : 0u) |
+                       ((order[k].flags & CSTRIPE_ORDER_NULLS_FIRST) ? TOPN_F_NFIRST : 0u) |
+                       ((t == CSTRIPE_F32 || t == CSTRIPE_F64) ? TOPN_F_FLOAT : 0u);
+    }
+
+    SelectParams sp{};
+    uint8_t widths[MAX_PROJ] = {0};
+    uint32_t dst_col[MAX_PROJ] = {0};
+    for (uint32_t c = 0; c < n_cols && out->col_values; c++) {
+        if (!out->col_values[c]) continue;
+        const int pj = g->proj_of_col[c];
+        if (pj < 0) { cs_set_err("scan_select_topn: column %u not projected", c); return CSTRIPE_ERR_ARG; }
+        widths[sp.n_cols] = (uint8_t)csf_type_width(r->cols[c].type);
+        dst_col[sp.n_cols] = c;
+        sp.cols[sp.n_cols].proj = (uint32_t)pj;
+        sp.n_cols++;
+    }
+
+    /* key packing: per column [ord(lo), ord(hi)] from the SELECTED chunk
+     * groups' skip nodes (ints biased to unsigned, floats through
+     * topn_f64_ord — their min/max are recorded in PG order already);
+     * bitlen(span + 1) bits hold the value offsets and one NULL code */
+    uint32_t kbits[CSTRIPE_MAX_ORDER_COLS] = {0};
+    uint32_t total_bits = 0;
+    for (uint32_t k = 0; k < n_order; k++) {
+        const uint32_t col = order[k].column;
+        const uint8_t t = otype[k];
+        const bool is_f = (tp.kflags[k] & TOPN_F_FLOAT) != 0;
+        auto ord_i = [](int64_t v) -> uint64_t { return (uint64_t)v ^ TOPN_SIGN; };
+        auto ord_node = [&](int64_t bits_or_val) -> uint64_t {
+            if (!is_f) return ord_i(bits_or_val);
+            double d;
+            memcpy(&d, &bits_or_val, 8);
+            return topn_f64_ord(d);
+        };
+        uint64_t olo = 0, ohi = 0;
+        bool any = false, full = false;
+        if (t == CSTRIPE_VARTEXT) {
+            /* dictionary ranks: exactly [0, n_dict - 1] */
+            const int64_t nd = (int64_t)s->text_dicts[col].offsets.size() - 1;
+            olo = ord_i(0);
+            ohi = ord_i(nd > 0 ? nd - 1 : 0);
+        } else {
+            for (const cs_selchunk &sc : s->sel) {
+                const csf_skipnode &nd = r->stripes[sc.stripe].nodes[col][sc.chunk].n;
+                if (nd.has_min_max) {
+                    const uint64_t a = ord_node(nd.min_i), b = ord_node(nd.max_i);
+                    if (!any) { olo = a; ohi = b; any = true; }
+                    else { olo = std::min(olo, a); ohi = std::max(ohi, b); }
+                } else if (nd.n_present > 0) {
+                    full = true;
+                }
+            }
+            if (full) {
+                switch (t) {
+                    case CSTRIPE_I8:  olo = ord_i(INT8_MIN);  ohi = ord_i(INT8_MAX);  break;
+                    case CSTRIPE_I16: olo = ord_i(INT16_MIN); ohi = ord_i(INT16_MAX); break;
+                    case CSTRIPE_I32: olo = ord_i(INT32_MIN); ohi = ord_i(INT32_MAX); break;
+                    case CSTRIPE_I64: olo = ord_i(INT64_MIN); ohi = ord_i(INT64_MAX); break;
+                    default:
+                        olo = topn_f64_ord(-__builtin_inf());
+                        ohi = topn_f64_ord(__builtin_nan(""));
+                        break;
+                }
+            }
+            if (ohi < olo) { olo = 0; ohi = 0; }
+        }
+        tp.klo[k] = olo;
+        tp.kspan[k] = ohi - olo;
+        kbits[k] = tp.kspan[k] == ~0ull ? 65u : hash_bitlen(tp.kspan[k] + 1);
+        total_bits += kbits[k];
+    }
+    if (total_bits > 64) {
+        char msg[160];
+        int w = 0;
+        for (uint32_t k = 0; k < n_order; k++)
+            w += snprintf(msg + w, sizeof(msg) - (size_t)w, "%scol %u: %u bits",
+                          k ? ", " : "", order[k].column, kbits[k]);
+        cs_set_err("scan_select_topn: packed key needs %u bits > 64 (%s) — key ranges "
+                   "come from the selected chunk groups' min/max", total_bits, msg);
+        return CSTRIPE_ERR_ARG;
+    }
+    /* column 0 most significant */
+    for (uint32_t k = n_order, sh = 0; k-- > 0;) {
+        tp.kshift[k] = sh;
+        sh += kbits[k];
+    }
+
+    AggParams p{};
+    { int _rc = select_prepare(s, p); if (_rc != CSTRIPE_OK) return _rc; }
+    sp.tiles_per_group = p.tiles_per_group;
+    tp.tiles_per_group = p.tiles_per_group;
+    if (g->n_groups == 0) {
+        topn_zero_timing(s);
+        out->n_rows = 0;
+        return CSTRIPE_OK;
+    }
+    for (hipEvent_t &e : g->tev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+
+    float ms_d = 0, ms_m = 0, ms_o = 0;
+    bool decoded = false;
+    if (!g->sel_cached) {
+        { int _rc = select_run_count(s, p); if (_rc != CSTRIPE_OK) return _rc; }
+        ms_d = (float)s->last_decode_ms;
+        ms_m = (float)s->last_select_mask_ms;
+        ms_o = (float)s->last_select_offsets_ms;
+        decoded = true;     /* same stream, nothing in between */
+    }
+    const uint64_t n_pass = g->sel_total;
+    s->last_select_mask_ms = ms_m;
+    s->last_select_offsets_ms = ms_o;
+    s->last_select_emit_ms = 0;
+    s->last_agg_ms = 0;
+    if (n_pass == 0) {
+        s->last_decode_ms = ms_d;
+        s->last_kernel_ms = ms_d + ms_m + ms_o;
+        s->last_topn_key_ms = s->last_topn_select_ms = s->last_topn_emit_ms = 0;
+        out->n_rows = 0;
+        return CSTRIPE_OK;
+    }
+    const uint64_t m = std::min<uint64_t>(limit, n_pass);
+    const bool selecting = n_pass > limit;
+    const uint32_t n_tiles = g->n_groups * p.tiles_per_group;
+    tp.n_keys = n_pass;
+
+    /* scan-order rows (emit) and, in host mode, the permuted staging */
+    uint64_t off_vals[MAX_PROJ], off_nulls[MAX_PROJ], off_rn = 0, need = 0;
+    bool want_nulls[MAX_PROJ];
+    for (uint32_t i = 0; i < sp.n_cols; i++) {
+        want_nulls[i] = out->col_nulls && out->col_nulls[dst_col[i]];
+        off_vals[i] = need;
+        need = align_up(need + m * widths[i], 16);
+        off_nulls[i] = need;
+        if (want_nulls[i]) need = align_up(need + m, 16);
+    }
+    off_rn = need;
+    if (out->row_numbers) need += m * sizeof(uint64_t);
+    if (need == 0) need = 16;
+
+    { int _rc = hash_grow(g->d_tn_keys, g->tn_keys_n, n_pass); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_tn_emit, g->tn_emit_bytes, need); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_tn_perm, g->tn_perm_n, m); if (_rc != CSTRIPE_OK) return _rc; }
+    if (!dst_on_device) { int _rc = hash_grow(g->d_tn_out, g->tn_out_bytes, need); if (_rc != CSTRIPE_OK) return _rc; }
+    if (selecting) {
+        const uint64_t words = (uint64_t)n_tiles * SEL_SLICES;
+        { int _rc = hash_grow(g->d_tn_okeys, g->tn_okeys_n, m); if (_rc != CSTRIPE_OK) return _rc; }
+        { int _rc = hash_grow(g->d_tn_mask, g->tn_mask_n, words); if (_rc != CSTRIPE_OK) return _rc; }
+        { int _rc = hash_grow(g->d_tn_eq, g->tn_eq_n, words); if (_rc != CSTRIPE_OK) return _rc; }
+        { int _rc = hash_grow(g->d_tn_counts, g->tn_counts_n, (uint64_t)n_tiles); if (_rc != CSTRIPE_OK) return _rc; }
+        { int _rc = hash_grow(g->d_tn_tbases, g->tn_tbases_n, (uint64_t)n_tiles); if (_rc != CSTRIPE_OK) return _rc; }
+        { int _rc = hash_grow(g->d_tn_bases, g->tn_bases_n, (uint64_t)n_tiles); if (_rc != CSTRIPE_OK) return _rc; }
+        if (!g->d_tn_state) HIP_TRY(hipMalloc(&g->d_tn_state, sizeof(TopnState)));
+        if (!g->d_tn_total) HIP_TRY(hipMalloc(&g->d_tn_total, 2 * sizeof(uint64_t)));
+    }
+
+    HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+    HIP_TRY(hipEventRecord(g->tev[0], g->stream));
+    if (!decoded) { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+    HIP_TRY(hipEventRecord(g->tev[1], g->stream));
+    hipLaunchKernelGGL(topn_key_kernel, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_data, g->d_scratch, g->d_rank, g->d_groups, g->d_colloc,
+                       g->d_sel_mask, g->d_sel_bases, g->d_tn_keys, g->d_error, tp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->tev[2], g->stream));
+    if (selecting) {
+        const uint32_t rounds = (total_bits + 7) / 8;       /* 1..8 */
+        const uint64_t kblocks = (n_pass + AGG_BLOCK - 1) / AGG_BLOCK;
+        const uint32_t hgrid = (uint32_t)std::min<uint64_t>(kblocks, TOPN_GRID);
+        hipLaunchKernelGGL(topn_init_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_tn_state, limit);
+        for (uint32_t rd = 0; rd < rounds; rd++) {
+            const uint32_t shift = 8 * (rounds - 1 - rd);
+            hipLaunchKernelGGL(topn_hist_kernel, dim3(hgrid), dim3(AGG_BLOCK), 0, g->stream,
+                               g->d_tn_keys, n_pass, g->d_tn_state, shift);
+            hipLaunchKernelGGL(topn_pick_kernel, dim3(1), dim3(WAVE), 0, g->stream,
+                               g->d_tn_state);
+        }
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(topn_refine_kernel, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_sel_mask, g->d_sel_bases, g->d_tn_keys, n_pass,
+                           g->d_tn_state, g->d_tn_mask, g->d_tn_eq, g->d_tn_counts);
+        hipLaunchKernelGGL(select_offsets_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_tn_counts, g->d_tn_tbases, g->d_tn_total, n_tiles);
+        hipLaunchKernelGGL(topn_final_kernel, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_tn_eq, g->d_tn_tbases, g->d_tn_state, g->d_tn_mask,
+                           g->d_tn_counts);
+        hipLaunchKernelGGL(select_offsets_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_tn_counts, g->d_tn_bases, g->d_tn_total + 1, n_tiles);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(g->tev[3], g->stream));
+
+    /* one sync before anything is emitted: the range flag, and the refined
+     * total, which must be exactly `limit` — the emit buffers are sized by it */
+    int h_err = 0;
+    uint64_t h_tot[2] = {0, m};
+    HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    if (selecting)
+        HIP_TRY(hipMemcpyAsync(h_tot, g->d_tn_total, sizeof(h_tot), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (h_err & TOPN_ERR_RANGE) {
+        cs_set_err("scan_select_topn: an order value lies outside its chunk's recorded min/max "
+                   "(device flag %d) — corrupt skip nodes", h_err);
+        return CSTRIPE_ERR_FORMAT;
+    }
+    if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    if (h_tot[1] != m) {
+        cs_set_err("scan_select_topn: selection kept %llu rows, expected %llu",
+                   (unsigned long long)h_tot[1], (unsigned long long)m);
+        return CSTRIPE_ERR;
+    }
+
+    for (uint32_t i = 0; i < sp.n_cols; i++) {
+        sp.cols[i].vals = g->d_tn_emit + off_vals[i];
+        sp.cols[i].nulls = want_nulls[i] ? g->d_tn_emit + off_nulls[i] : nullptr;
+    }
+    sp.row_numbers = out->row_numbers ? (uint64_t *)(g->d_tn_emit + off_rn) : nullptr;
+    HIP_TRY(hipEventRecord(g->tev[4], g->stream));
+    hipLaunchKernelGGL(select_emit_kernel, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_data, g->d_scratch, g->d_rank, g->d_groups, g->d_colloc,
+                       selecting ? g->d_tn_mask : g->d_sel_mask,
+                       selecting ? g->d_tn_bases : g->d_sel_bases, g->d_sel_rowbase, sp);
+    if (selecting)
+        hipLaunchKernelGGL(topn_keygather_kernel, dim3(n_tiles), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_sel_mask, g->d_sel_bases, g->d_tn_mask, g->d_tn_bases,
+                           g->d_tn_keys, n_pass, g->d_tn_okeys, m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->tev[5], g->stream));
+
+    /* the m (key, ordinal) pairs: ordinals are scan order, so a stable sort
+     * by key is the sort by (key, row number) */
+    std::vector<uint64_t> h_keys(m);
+    HIP_TRY(hipMemcpyAsync(h_keys.data(), selecting ? g->d_tn_okeys : g->d_tn_keys,
+                           m * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    std::vector<uint32_t> h_perm(m);
+    for (uint64_t i = 0; i < m; i++) h_perm[i] = (uint32_t)i;
+    std::stable_sort(h_perm.begin(), h_perm.end(),
+                     [&](uint32_t a, uint32_t b) { return h_keys[a] < h_keys[b]; });
+    HIP_TRY(hipMemcpyAsync(g->d_tn_perm, h_perm.data(), m * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, g->stream));
+
+    PermParams pp{};
+    pp.n_cols = sp.n_cols;
+    pp.n = m;
+    for (uint32_t i = 0; i < sp.n_cols; i++) {
+        PermCol &pc = pp.cols[i];
+        pc.width = widths[i];
+        pc.src_vals = sp.cols[i].vals;
+        pc.src_nulls = sp.cols[i].nulls;
+        if (dst_on_device) {
+            pc.dst_vals = (uint8_t *)out->col_values[dst_col[i]];
+            pc.dst_nulls = want_nulls[i] ? out->col_nulls[dst_col[i]] : nullptr;
+        } else {
+            pc.dst_vals = g->d_tn_out + off_vals[i];
+            pc.dst_nulls = want_nulls[i] ? g->d_tn_out + off_nulls[i] : nullptr;
+        }
+    }
+    pp.src_rn = sp.row_numbers;
+    pp.dst_rn = !out->row_numbers ? nullptr
+              : dst_on_device ? out->row_numbers : (uint64_t *)(g->d_tn_out + off_rn);
+    const uint32_t pgrid = (uint32_t)std::min<uint64_t>((m + AGG_BLOCK - 1) / AGG_BLOCK, TOPN_GRID);
+    HIP_TRY(hipEventRecord(g->tev[6], g->stream));
+    hipLaunchKernelGGL(topn_permute_kernel, dim3(pgrid), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_tn_perm, pp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->tev[7], g->stream));
+    if (!dst_on_device) {
+        for (uint32_t i = 0; i < sp.n_cols; i++) {
+            HIP_TRY(hipMemcpyAsync(out->col_values[dst_col[i]], pp.cols[i].dst_vals,
+                                   m * widths[i], hipMemcpyDeviceToHost, g->stream));
+            if (want_nulls[i])
+                HIP_TRY(hipMemcpyAsync(out->col_nulls[dst_col[i]], pp.cols[i].dst_nulls,
+                                       m, hipMemcpyDeviceToHost, g->stream));
+        }
+        if (pp.dst_rn)
+            HIP_TRY(hipMemcpyAsync(out->row_numbers, pp.dst_rn, m * sizeof(uint64_t),
+                                   hipMemcpyDeviceToHost, g->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(g->stream));   /* h_perm leaves scope */
+
+    float ms_d2 = 0, ms_k = 0, ms_s = 0, ms_e = 0, ms_p = 0;
+    (void)hipEventElapsedTime(&ms_d2, g->tev[0], g->tev[1]);
+    (void)hipEventElapsedTime(&ms_k, g->tev[1], g->tev[2]);
+    (void)hipEventElapsedTime(&ms_s, g->tev[2], g->tev[3]);
+    (void)hipEventElapsedTime(&ms_e, g->tev[4], g->tev[5]);
+    (void)hipEventElapsedTime(&ms_p, g->tev[6], g->tev[7]);
+    s->last_decode_ms = ms_d + ms_d2;
+    s->last_topn_key_ms = ms_k;
+    if (!selecting) ms_s = 0;           /* nothing ran between the two events */
+    s->last_topn_select_ms = ms_s;
+    s->last_topn_emit_ms = ms_e + ms_p;
+    s->last_kernel_ms = ms_d + ms_d2 + ms_m + ms_o + ms_k + ms_s + ms_e + ms_p;
+    out->n_rows = m;
     return CSTRIPE_OK;
 }
 

@@ -1591,6 +1591,25 @@ extern "C" int cstripe_scan_last_select_ms(const cstripe_scan *s, double *mask_m
     return CSTRIPE_OK;
 }
 
+extern "C" int cstripe_scan_select_topn(cstripe_scan *s, const cstripe_order_key *order,
+                                        uint32_t n_order, uint64_t limit,
+                                        cstripe_rows *out, int dst_on_device)
+{
+    if (!s) { cs_set_err("scan_select_topn: bad args"); return CSTRIPE_ERR_ARG; }
+    /* the staged check comes first; argument checks follow it there */
+    return csgpu_select_topn(s, order, n_order, limit, out, dst_on_device);
+}
+
+extern "C" int cstripe_scan_last_topn_ms(const cstripe_scan *s, double *key_ms,
+                                         double *select_ms, double *emit_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (key_ms) *key_ms = s->last_topn_key_ms;
+    if (select_ms) *select_ms = s->last_topn_select_ms;
+    if (emit_ms) *emit_ms = s->last_topn_emit_ms;
+    return CSTRIPE_OK;
+}
+
 extern "C" int cstripe_scan_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs,
                                        uint32_t n_aggs, const uint32_t *key_cols,
                                        uint32_t n_key_cols, uint64_t capacity,

@@ -87,6 +87,9 @@ struct cstripe_scan {
     double last_hash_init_ms = 0.0;       /* scan_agg_hashed per-kernel split */
     double last_hash_scan_ms = 0.0;
     double last_hash_compact_ms = 0.0;
+    double last_topn_key_ms = 0.0;        /* scan_select_topn per-stage split */
+    double last_topn_select_ms = 0.0;
+    double last_topn_emit_ms = 0.0;
     /* random-access read cache (the reference keeps the current stripe
      * open across ColumnarReadRowByRowNumber calls the same way) */
     int64_t rr_gi = -1;
@@ -122,6 +125,11 @@ int  csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
 int  csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
                       const uint32_t *key_cols, uint32_t n_key_cols,
                       uint64_t capacity, cstripe_hgroups *out);
+/* ORDER BY ... LIMIT (key build -> radix select -> refine -> emit ->
+ * permute); reads the select cache, writes only its own buffers */
+int  csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order,
+                       uint32_t n_order, uint64_t limit, cstripe_rows *out,
+                       int dst_on_device);
 
 /* device write path: one chunk's columns compressed on the GPU (canonical
  * parses where the data fits, raw copy-back otherwise) */

@@ -512,6 +512,73 @@ int cstripe_scan_select(cstripe_scan *s, cstripe_rows *out,
 int cstripe_scan_last_select_ms(const cstripe_scan *s, double *mask_ms,
                                 double *offsets_ms, double *emit_ms);
 
+/* ---- ORDER BY ... LIMIT over the scan (device top-N) ----
+ * What the reference pushes to every worker: WorkerLimitCount and
+ * WorkerSortClauseList (multi_logical_optimizer.c:5038-5212) hand each shard
+ * ORDER BY ... LIMIT limit+offset, and the coordinator re-sorts the few rows
+ * it gets back. The device finds the limit-th smallest key without sorting
+ * (an 8-bit-per-round radix select) and compacts exactly those rows. */
+#define CSTRIPE_MAX_ORDER_COLS    4
+#define CSTRIPE_MAX_TOPN          (1u << 20)
+#define CSTRIPE_ORDER_DESC        1u
+#define CSTRIPE_ORDER_NULLS_FIRST 2u     /* absent = NULLS LAST */
+typedef struct cstripe_order_key { uint32_t column; uint32_t flags; } cstripe_order_key;
+
+/* cstripe_scan_select_topn:
+ *  - Rows: those that pass the scan's CNF, evaluated exactly as
+ *    cstripe_scan_select evaluates it; chunk groups removed by min/max
+ *    pruning contribute nothing. out->n_rows = min(limit, passing rows).
+ *    Every destination in `out` holds `limit` entries. Values, NULL
+ *    zero-fill, null bytes, row numbers and device / host destinations
+ *    follow cstripe_scan_select; a wanted column must be projected.
+ *  - Order: lexicographic over order[0..n_order), each column ascending, or
+ *    descending with CSTRIPE_ORDER_DESC. NULLs sort after every value of the
+ *    column, or before it with CSTRIPE_ORDER_NULLS_FIRST — the flag is taken
+ *    literally (PG's defaults, ASC -> LAST and DESC -> FIRST, are the
+ *    caller's job). Integers compare signed; F32/F64 compare in PG order
+ *    (NaN greatest and equal to itself, -0.0 = +0.0); VARTEXT compares by
+ *    dictionary rank, which is memcmp order. Rows equal on the whole key
+ *    tuple come out in ascending row number, so the result is fully
+ *    determined and identical on every call.
+ *  - Key types: I8/I16/I32/I64/F32/F64/VARTEXT. A TEXT order column is
+ *    CSTRIPE_ERR_ARG: its row-level order in this ABI is whole-slot, not
+ *    collation, and the message says so.
+ *  - Key packing (the supported domain): as in cstripe_scan_agg_hashed the
+ *    key tuple is ONE 64-bit word. Per column [lo, hi] comes from the skip
+ *    nodes (min/max) of the scan's SELECTED chunk groups; a selected chunk
+ *    with present values and no min/max widens the column to its type's full
+ *    range; VARTEXT uses [0, n_dict - 1]. Floats go through an
+ *    order-preserving map `ord` of the f64 bit pattern (F32 widened exactly;
+ *    every NaN maps to ord(+inf) + 1, -0.0 to +0.0; the skip nodes' float
+ *    min/max are already in PG order). A column needs
+ *    bitlen(ord(hi) - ord(lo) + 1) bits: the value offsets plus one NULL
+ *    code at either end. Column 0 is most significant. A total above 64 bits
+ *    is CSTRIPE_ERR_ARG, the message naming each column's bits. A value
+ *    outside [lo, hi] (a file whose skip nodes lie) raises a device flag and
+ *    returns CSTRIPE_ERR_FORMAT, never a wrong row.
+ *  - Errors: an unstaged scan returns CSTRIPE_ERR_NOGPU, checked first,
+ *    before any argument. CSTRIPE_ERR_ARG: limit 0 or above
+ *    CSTRIPE_MAX_TOPN, n_order 0 or above CSTRIPE_MAX_ORDER_COLS, an order
+ *    column out of range or not projected, a repeated order column. Zero
+ *    selected chunk groups or zero passing rows: CSTRIPE_OK, n_rows = 0.
+ *  - Memory: the device key array costs 8 bytes per PASSING row (not per
+ *    returned row), plus two mask bits per scanned row; both hang off the
+ *    scan, grow on demand and are freed by cstripe_scan_end.
+ *  - Re-invocable, and may be interleaved with every other scan call
+ *    without changing any of their results: it uses (and, when absent,
+ *    fills) the pass mask, tile counts and bases cstripe_scan_select caches,
+ *    and never writes into them — its refined mask and bases live in
+ *    buffers of their own. cstripe_scan_last_kernel_ms /
+ *    cstripe_scan_last_decode_kernel_ms then report this call;
+ *    cstripe_scan_last_topn_ms splits out the key build, the selection (all
+ *    histogram, pick and refine launches; 0 when passing rows <= limit) and
+ *    the final emit plus permute. Any out pointer may be NULL. */
+int cstripe_scan_select_topn(cstripe_scan *s, const cstripe_order_key *order,
+                             uint32_t n_order, uint64_t limit,
+                             cstripe_rows *out, int dst_on_device);
+int cstripe_scan_last_topn_ms(const cstripe_scan *s, double *key_ms,
+                              double *select_ms, double *emit_ms);
+
 /* ---- hashed GROUP BY (device hash aggregate over integer keys) ----
  * The worker side of the reference's general grouped plan: HashAggregate
  * over ColumnarScan, one partial row per group, then a per-group coordinator
