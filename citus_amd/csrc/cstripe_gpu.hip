@@ -97,7 +97,6 @@ struct AggParams {
 };
 
 struct FusedTile;
-struct FusedTileG;
 
 /* per-block / final accumulator cell (32 B) */
 struct AccCell {
@@ -132,8 +131,6 @@ struct cs_gpu_state {
     uint32_t max_zseg_comp = 0;      /* largest zstd frame (LDS-variant gate) */
     uint32_t max_zseg_dlen = 0;      /* largest zstd frame decompressed */
     zr_dtables *d_zrtab = nullptr;   /* predefined FSE decode tables */
-    uint32_t *d_segstart = nullptr;  /* per (group, proj): first d_segs index */
-    uint64_t greedy256_mask = 0;     /* proj cols stored as uniform 256B lz4 */
     std::vector<uint8_t> col_scratch;/* per proj: any chunk lands in scratch */
     int *d_error = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
@@ -188,16 +185,9 @@ struct cs_gpu_state {
     uint32_t max_seg_dlen = 0;
     bool segs_16aligned = true;
     bool fusable = true;             /* all proj cols dense i64, uniform 256B lz4 segs */
-    bool fusable_mixed = true;       /* widths in {1,8}; enables fused grouped */
     bool all_dense = true;           /* no NULLs anywhere -> pair_agg_kernel */
-    bool all_canonP = true;          /* every col canonical P/CONST -> lds kernel */
     struct FusedTile *d_tiles = nullptr;
     uint32_t n_tiles = 0;
-    struct FusedTileG *d_tiles2 = nullptr;
-    uint32_t n_tiles2 = 0;
-    uint16_t flane_base[8] = {0};
-    uint8_t fwidth[8] = {0};
-    uint16_t flanes_total = 0;
     uint32_t n_groups = 0;
     uint32_t n_proj = 0;
     uint32_t max_blocks = 0;
@@ -1369,176 +1359,6 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel(
     }
 }
 
-/* =====================================================================
- * LDS-staged scan (experimental variant): the R-row kernel is latency
- * bound (SQ_WAIT_ANY ~72% of wave cycles even at 8 waves/SIMD). Here each
- * block BULK-LOADS its tile's canonical predicate streams into LDS with
- * coalesced dwordx4 loads (deep MLP, few waits), then rows extract values
- * at LDS latency. Aggregate operand columns stay in global memory behind
- * the wave-uniform ballot (rarely touched at Q6 selectivity).
- * Eligible when every projected column is dense canonical P/CONST.
- * ===================================================================== */
-
-#define LDSK_TILE 2048
-
-template <int NPREDS, int NAGGS>
-__global__ __launch_bounds__(AGG_BLOCK) void lds_agg_kernel(
-    const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
-    const GroupDesc *__restrict__ groups, const ColLoc *__restrict__ colloc,
-    AccCell *__restrict__ block_out, uint32_t tiles2_per_group,
-    const AggParams params)
-{
-    const uint32_t n_preds = NPREDS >= 0 ? (uint32_t)NPREDS : params.n_preds;
-    const uint32_t n_aggs = NAGGS >= 0 ? (uint32_t)NAGGS : params.n_aggs;
-    const uint32_t gid = blockIdx.x / tiles2_per_group;
-    const uint32_t tile = blockIdx.x % tiles2_per_group;
-    const GroupDesc g = groups[gid];
-    const ColLoc *cols = colloc + g.colbase;
-
-    const uint32_t row_start = tile * LDSK_TILE;
-    if (row_start >= g.row_count) {     /* empty tile: zero partials */
-        if (threadIdx.x == 0)
-            for (uint32_t a = 0; a < n_aggs; a++) {
-                AccCell c{0, 0, 0.0, 0};
-                ThreadAcc z;
-                acc_init(z, params.aggs[a].kind);
-                c.lo = z.lo; c.hi = z.hi; c.f = z.f; c.cnt = 0;
-                block_out[(uint64_t)blockIdx.x * n_aggs + a] = c;
-            }
-        return;
-    }
-    const uint32_t row_end = min(row_start + LDSK_TILE, g.row_count);
-
-    extern __shared__ uint8_t sld[];
-
-    /* distinct predicate columns (wave-uniform bookkeeping) */
-    uint32_t pcols[4];
-    uint32_t npc = 0;
-    for (uint32_t p = 0; p < n_preds; p++) {
-        const uint32_t pj = params.preds[p].proj;
-        bool seen = false;
-        for (uint32_t i = 0; i < npc; i++) seen |= pcols[i] == pj;
-        if (!seen && npc < 4) pcols[npc++] = pj;
-    }
-
-    /* phase A: stage each pred column's stream window (uniform control) */
-    uint32_t roff[4], rdelta[4], rstep[4], rstart_pos[4];
-    uint64_t rmask[4], rhval[4];
-    uint8_t rmode[4];
-    uint32_t lds_used = 0;
-    for (uint32_t i = 0; i < npc; i++) {
-        const ColLoc cl = cols[pcols[i]];
-        rmode[i] = cl.mode;
-        rhval[i] = (uint64_t)cl.hval;
-        if (cl.mode == CSF_SEGMODE_CONST) {
-            roff[i] = 0; rdelta[i] = 0; rstep[i] = 0; rstart_pos[i] = 0;
-            rmask[i] = 0;
-            continue;
-        }
-        const uint32_t Lx = cl.L, step = Lx + 3u;
-        rstep[i] = step;
-        rmask[i] = (~0ull) >> ((8u - Lx) * 8u);
-        const uint32_t p0 = tile == 0 ? 0u
-                            : row_start * step + (6u - Lx);
-        rstart_pos[i] = p0;
-        const uint64_t src0 = cl.val_off + p0;
-        const uint64_t asrc = src0 & ~15ull;
-        rdelta[i] = (uint32_t)(src0 - asrc);
-        const uint32_t last_pos = (row_end - 1) * step + (6u - Lx);
-        const uint32_t nbytes = (uint32_t)(cl.val_off + last_pos + 8 - asrc + 15) & ~15u;
-        roff[i] = lds_used;
-        /* cooperative 16B copy */
-        const uint4 *gsrc = (const uint4 *)(data + asrc);
-        uint4 *ldst = (uint4 *)(sld + lds_used);
-        for (uint32_t o = threadIdx.x; o < (nbytes >> 4); o += AGG_BLOCK)
-            ldst[o] = gsrc[o];
-        lds_used += nbytes;
-    }
-    __syncthreads();
-
-    ThreadAcc acc[NAGGS >= 0 ? NAGGS : MAX_AGGS];
-    #pragma unroll
-    for (uint32_t a = 0; a < n_aggs; a++) acc_init(acc[a], params.aggs[a].kind);
-
-    /* extraction from LDS: value j of pred-col slot i */
-    auto lval = [&](uint32_t i, uint32_t j) -> int64_t {
-        if (rmode[i] == CSF_SEGMODE_CONST) return (int64_t)rhval[i];
-        uint32_t pos = j * rstep[i] + (9u - rstep[i]);
-        pos = j == 0 ? 1u : (j == 1 ? 9u : pos);
-        const uint32_t rel = rdelta[i] + pos - rstart_pos[i];
-        const uint32_t *l32 = (const uint32_t *)(sld + roff[i]);
-        const uint32_t wi = rel >> 2, sh = (rel & 3u) * 8u;
-        uint64_t lo = ((uint64_t)l32[wi + 1] << 32) | l32[wi];
-        if (sh) lo = (lo >> sh) | ((uint64_t)l32[wi + 2] << (64u - sh));
-        return (int64_t)((lo & rmask[i]) | rhval[i]);
-    };
-
-    constexpr int R = LDSK_TILE / AGG_BLOCK;      /* 8 rows per thread */
-    const uint32_t my0 = row_start + threadIdx.x * R;
-    bool pv[R], gv[R];
-    #pragma unroll
-    for (int k = 0; k < R; k++) {
-        pv[k] = my0 + k < row_end;
-        gv[k] = false;
-    }
-    int64_t v[R];
-    int last_proj = -1;
-    if (my0 < row_end) {
-        #pragma unroll
-        for (uint32_t p = 0; p < n_preds; p++) {
-            const PredD &pr = params.preds[p];
-            if ((int)pr.proj != last_proj) {
-                uint32_t slot = 0;
-                for (uint32_t i = 0; i < npc; i++)
-                    if (pcols[i] == pr.proj) slot = i;
-                #pragma unroll
-                for (int k = 0; k < R; k++) v[k] = lval(slot, my0 + k);
-                last_proj = (int)pr.proj;
-            }
-            #pragma unroll
-            for (int k = 0; k < R; k++)
-                gv[k] = gv[k] | pred_eval(pr, v[k], 0.0);   /* canon P: ints */
-            if (pr.gend) {
-                #pragma unroll
-                for (int k = 0; k < R; k++) { pv[k] = pv[k] & gv[k]; gv[k] = false; }
-            }
-        }
-    } else {
-        #pragma unroll
-        for (int k = 0; k < R; k++) pv[k] = false;
-    }
-    bool any = false;
-    #pragma unroll
-    for (int k = 0; k < R; k++) any |= pv[k];
-    if (__ballot(any) != 0) {
-        /* lanes past row_end load a safe in-bounds base; pv masks them */
-        const uint32_t safe0 = my0 < row_end ? my0 : row_start;
-        #pragma unroll
-        for (uint32_t a = 0; a < n_aggs; a++)
-            acc_multi<R>(acc[a], params.aggs[a], data, scratch, cols, safe0, pv);
-    }
-
-    __shared__ ThreadAcc lred2[AGG_BLOCK / WAVE][MAX_AGGS];
-    const uint32_t wid = threadIdx.x / WAVE;
-    const uint32_t lane = threadIdx.x % WAVE;
-    #pragma unroll
-    for (uint32_t a = 0; a < n_aggs; a++) {
-        wave_reduce(acc[a], params.aggs[a].kind);
-        if (lane == 0) lred2[wid][a] = acc[a];
-    }
-    __syncthreads();
-    if (wid == 0) {
-        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
-            ThreadAcc r = lred2[0][a];
-            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
-                acc_merge(r, lred2[w][a], params.aggs[a].kind);
-            AccCell c;
-            c.lo = r.lo; c.hi = r.hi; c.f = r.f; c.cnt = r.cnt;
-            block_out[(uint64_t)blockIdx.x * n_aggs + a] = c;
-        }
-    }
-}
-
 /* per-row precomputed aggregate contribution: operands loaded ONCE per row,
  * so the per-distinct-key reduce rounds touch registers only */
 struct PrepAcc {
@@ -1617,11 +1437,6 @@ struct GroupParams {
     uint32_t n_group_cols;
     uint32_t gproj[CSTRIPE_MAX_GROUP_COLS];   /* projected slots of key cols */
     uint32_t n_work;                          /* n_groups * tiles_per_group */
-    /* multi_grouped fused key decode: key cols stored as uniform 256 B
-     * greedy-LZ4 segments are decoded into LDS inside the kernel (half-tile
-     * granularity) instead of a scratch round trip */
-    uint32_t kdec_mask;                       /* bit i: key col i from LDS */
-    uint32_t kwidth[CSTRIPE_MAX_GROUP_COLS];  /* value width of key col i */
 };
 
 
@@ -1745,11 +1560,10 @@ __device__ inline void acc_apply_value_atomic(ThreadAcc *cell, uint8_t kind,
     }
 }
 
-template <int NAGGS, int R, int MINW = 4>
-__global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_grouped_kernel(
+template <int NAGGS, int R>
+__global__ __launch_bounds__(AGG_BLOCK, 4) void multi_grouped_kernel(
     const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
     const GroupDesc *__restrict__ groups, const ColLoc *__restrict__ colloc,
-    const SegDesc *__restrict__ segs, const uint32_t *__restrict__ segstart,
     uint32_t *__restrict__ keys_out, AccCell *__restrict__ cells_out,
     int *__restrict__ err, const GroupParams gp)
 {
@@ -1764,20 +1578,6 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_grouped_kernel(
     __shared__ unsigned long long wcnt[AGG_BLOCK / WAVE][MGRP_SLOTS];
     extern __shared__ uint8_t mg_lds[];
     ThreadAcc *wacc = (ThreadAcc *)mg_lds;   /* [wave][slot][agg] */
-    /* fused key-decode regions follow the accumulator tables: per decoded
-     * key col, ceil(HALF*width/256) lanes x 280 B (the lane-decode stride) */
-    uint32_t kbase[CSTRIPE_MAX_GROUP_COLS] = {0, 0};
-    uint32_t ksegs_half[CSTRIPE_MAX_GROUP_COLS] = {0, 0};
-    {
-        uint32_t off = (uint32_t)(n_waves * MGRP_SLOTS * n_aggs * sizeof(ThreadAcc));
-        off = (off + 15u) & ~15u;
-        for (uint32_t i = 0; i < gp.n_group_cols; i++) {
-            if (!(gp.kdec_mask & (1u << i))) continue;
-            kbase[i] = off;
-            ksegs_half[i] = (HALF * gp.kwidth[i] + 255u) / 256u;
-            off += ksegs_half[i] * 280u;
-        }
-    }
 
     for (uint32_t i = threadIdx.x; i < n_waves * MGRP_SLOTS; i += AGG_BLOCK) {
         wkeys[i / MGRP_SLOTS][i % MGRP_SLOTS] = -1;
@@ -1805,31 +1605,6 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_grouped_kernel(
     for (uint32_t half_start = row_start; half_start < row_end;
          half_start += HALF) {
         const uint32_t half_end = min(half_start + HALF, row_end);
-
-        /* phase 1: decode this half's key-column segments into LDS (uniform
-         * 256 B greedy-LZ4 segments, one lane each) */
-        if (gp.kdec_mask) {
-            __syncthreads();           /* LDS regions reused across halves */
-            for (uint32_t i = 0; i < gp.n_group_cols; i++) {
-                if (!(gp.kdec_mask & (1u << i))) continue;
-                const uint32_t base_lane = i * 64u;
-                const uint32_t rows_half = half_end - half_start;
-                const uint32_t nseg = (rows_half * gp.kwidth[i] + 255u) / 256u;
-                const uint32_t k = threadIdx.x - base_lane;
-                if (threadIdx.x >= base_lane && k < nseg) {
-                    const uint32_t pj = gp.gproj[i];
-                    const uint32_t seg0 = segstart[(uint64_t)gid * params.n_proj + pj]
-                                          + (half_start * gp.kwidth[i]) / 256u;
-                    const SegDesc sd = segs[seg0 + k];
-                    lz4_lane_decode(data, sd,
-                                    mg_lds + kbase[i] + (size_t)k * 280u, err);
-                }
-            }
-            __syncthreads();
-        }
-
-        /* NOTE: no `continue` below this point — every thread must reach
-         * the next half's __syncthreads (the key-decode LDS is reused) */
         const uint32_t my0 = half_start + R * threadIdx.x;
         bool pv[R], gv[R];
         #pragma unroll
@@ -1862,8 +1637,8 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_grouped_kernel(
         for (int k = 0; k < R; k++) any |= pv[k];
         if (__ballot(any) != 0) {
 
-        /* group keys: LDS-decoded cols read at half-local offsets, others
-         * through col_multi; 9-bit enc (bit 8 = NULL never set: dense) */
+        /* group keys through col_multi; 9-bit enc (bit 8 = NULL never set:
+         * dense) */
         uint32_t key[R];
         {
             const uint32_t safe0 = my0 < half_end ? my0 : half_start;
@@ -1872,28 +1647,13 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_grouped_kernel(
             for (uint32_t i = 0; i < gp.n_group_cols; i++) {
                 const uint32_t pj = gp.gproj[i];
                 const bool is_text = cols[pj].type == CSTRIPE_TEXT;
-                if (gp.kdec_mask & (1u << i)) {
-                    const uint32_t kw = gp.kwidth[i];
-                    #pragma unroll
-                    for (int k = 0; k < R; k++) {
-                        const uint32_t r = (safe0 + k) - half_start;
-                        const uint32_t bo = r * kw;
-                        const uint8_t *pp2 = mg_lds + kbase[i]
-                                             + (bo >> 8) * 280u + (bo & 255u);
-                        uint32_t raw = kw == 4 ? *(const uint32_t *)pp2
-                                               : (uint32_t)*pp2;
-                        if (is_text) raw >>= 8;
-                        key[k] |= (raw & 0xFF) << (9 * i);
-                    }
-                } else {
-                    ValsR<R> kq;
-                    col_multi<R>(data, scratch, cols[pj], safe0, kq);
-                    #pragma unroll
-                    for (int k = 0; k < R; k++) {
-                        uint32_t raw = (uint32_t)kq.v[k];
-                        if (is_text) raw >>= 8;
-                        key[k] |= (raw & 0xFF) << (9 * i);
-                    }
+                ValsR<R> kq;
+                col_multi<R>(data, scratch, cols[pj], safe0, kq);
+                #pragma unroll
+                for (int k = 0; k < R; k++) {
+                    uint32_t raw = (uint32_t)kq.v[k];
+                    if (is_text) raw >>= 8;
+                    key[k] |= (raw & 0xFF) << (9 * i);
                 }
             }
         }
@@ -2179,164 +1939,6 @@ __global__ __launch_bounds__(AGG_BLOCK) void grouped_agg_kernel(
             }
         }
         for (uint32_t j = n; j < n_waves * GRP_SLOTS; j++) bk[j] = 0xFFFFFFFFu;
-    }
-}
-
-/* =====================================================================
- * FUSED GROUPED kernel (TPC-H Q1 shape): same no-scratch idea as
- * fused_agg_kernel, generalized to mixed i64/i8 columns — tile = 1536 rows
- * (1536*width is a multiple of 256 for both widths, so tile boundaries land
- * on segment boundaries), lane ranges per column by prefix. Groups
- * accumulate into ONE per-block 16-slot LDS table with the carry-exact
- * atomics; blocks grid-stride over tiles and flush their table once.
- * ===================================================================== */
-
-#define FUSEG_TILE_ROWS 1536
-#define FUSEG_SLOTS 16
-#define FUSEG_GRID 2048
-
-struct FusedTileG {
-    uint32_t row_count;
-    uint32_t seg_base[8];
-};
-
-struct FusedGParams {
-    AggParams base;
-    uint32_t n_group_cols;
-    uint32_t gproj[CSTRIPE_MAX_GROUP_COLS];
-    uint32_t n_tiles;
-    uint16_t lane_base[8];       /* per proj col: first LDS region */
-    uint8_t  width[8];           /* per proj col: value width (1 or 8) */
-    uint16_t lanes_total;
-};
-
-template <int NAGGS>
-__global__ __launch_bounds__(AGG_BLOCK) void fused_grouped_kernel(
-    const uint8_t *__restrict__ data, const SegDesc *__restrict__ segs,
-    const FusedTileG *__restrict__ tiles, uint32_t *__restrict__ keys_out,
-    AccCell *__restrict__ cells_out, int *__restrict__ err,
-    const FusedGParams gp)
-{
-    const AggParams &params = gp.base;
-    const uint32_t n_aggs_ct = NAGGS >= 0 ? (uint32_t)NAGGS : params.n_aggs;
-    const uint32_t tid = threadIdx.x;
-    extern __shared__ uint8_t lds[];
-    int *skeys = (int *)(lds + (size_t)gp.lanes_total * FUSE_STRIDE);
-    ThreadAcc *scells = (ThreadAcc *)(skeys + FUSEG_SLOTS);
-
-    for (uint32_t i = tid; i < FUSEG_SLOTS; i += AGG_BLOCK) {
-        skeys[i] = -1;
-        for (uint32_t a = 0; a < n_aggs_ct; a++)
-            acc_init(scells[i * n_aggs_ct + a], params.aggs[a].kind);
-    }
-    __syncthreads();
-
-    /* my (col, seg) assignment: first col whose lane range contains tid */
-    uint32_t mycol = 0xFFFFFFFF, myseg = 0;
-    for (uint32_t c2 = 0; c2 < params.n_proj; c2++) {
-        uint32_t base = gp.lane_base[c2];
-        uint32_t span = (uint32_t)FUSEG_TILE_ROWS * gp.width[c2] / 256;
-        if (tid >= base && tid < base + span) { mycol = c2; myseg = tid - base; }
-    }
-
-    auto val = [&](uint32_t proj, uint32_t row) -> int64_t {
-        const uint32_t byteoff = row * gp.width[proj];
-        const uint8_t *p = lds + ((size_t)gp.lane_base[proj] + (byteoff >> 8)) * FUSE_STRIDE
-                           + (byteoff & 255);
-        return gp.width[proj] == 8 ? *(const int64_t *)p : (int64_t)*(const int8_t *)p;
-    };
-
-    /* per-lane register key->slot cache */
-    uint32_t ck0 = ~0u, ck1 = ~0u;
-    uint32_t cs0 = 0, cs1 = 0;
-
-    for (uint32_t work = blockIdx.x; work < gp.n_tiles; work += gridDim.x) {
-        const FusedTileG t = tiles[work];
-
-        /* phase 1: decode */
-        if (mycol != 0xFFFFFFFF) {
-            const uint32_t nsegs = (t.row_count * gp.width[mycol] + 255) >> 8;
-            if (myseg < nsegs) {
-                const SegDesc sd = segs[t.seg_base[mycol] + myseg];
-                lz4_lane_decode(data, sd, lds + (size_t)tid * FUSE_STRIDE, err);
-            }
-        }
-        __syncthreads();
-
-        /* phase 2: filter + group + accumulate */
-        for (uint32_t row = tid; row < t.row_count; row += AGG_BLOCK) {
-            bool pass = true, gv = false;
-            int last_proj = -1;
-            int64_t liv = 0;
-            for (uint32_t p = 0; p < params.n_preds; p++) {
-                const PredD &pr = params.preds[p];
-                if ((int)pr.proj != last_proj) { liv = val(pr.proj, row); last_proj = (int)pr.proj; }
-                gv = gv | pred_eval(pr, liv, 0.0);
-                if (pr.gend) { pass = pass & gv; gv = false; }
-            }
-            if (!pass) continue;
-            uint32_t key = 0;
-            for (uint32_t gc = 0; gc < gp.n_group_cols; gc++)
-                key |= ((uint32_t)val(gp.gproj[gc], row) & 0xFF) << (9 * gc);
-            uint32_t slot = 0xFFFFFFFF;
-            if (key == ck0) slot = cs0;
-            else if (key == ck1) slot = cs1;
-            else {
-                for (uint32_t s2 = 0; s2 < FUSEG_SLOTS; s2++) {
-                    int old = atomicCAS(&skeys[s2], -1, (int)key);
-                    if (old == -1 || old == (int)key) { slot = s2; break; }
-                }
-                if (slot == 0xFFFFFFFF) { atomicOr(err, 8); continue; }
-                ck1 = ck0; cs1 = cs0;
-                ck0 = key; cs0 = slot;
-            }
-            for (uint32_t a = 0; a < n_aggs_ct; a++) {
-                const AggD &g = params.aggs[a];
-                PrepAcc p2;
-                p2.valid = true; p2.f = 0.0; p2.hi = 0;
-                switch (g.kind) {
-                    case CSTRIPE_AGG_COUNT_STAR:
-                    case CSTRIPE_AGG_COUNT_COL: p2.lo = 1; break;
-                    case CSTRIPE_AGG_SUM_I64:
-                    case CSTRIPE_AGG_MIN_I64:
-                    case CSTRIPE_AGG_MAX_I64: {
-                        int64_t v = val(g.proj_a, row);
-                        p2.lo = v; p2.hi = v < 0 ? -1 : 0; break;
-                    }
-                    case CSTRIPE_AGG_SUM_PROD_I64: {
-                        __int128 x = (__int128)val(g.proj_a, row) * val(g.proj_b, row);
-                        p2.lo = (int64_t)(uint64_t)x; p2.hi = (int64_t)(x >> 64); break;
-                    }
-                    case CSTRIPE_AGG_SUM_DISC_I64: {
-                        __int128 x = (__int128)val(g.proj_a, row) * (g.one - val(g.proj_b, row));
-                        p2.lo = (int64_t)(uint64_t)x; p2.hi = (int64_t)(x >> 64); break;
-                    }
-                    case CSTRIPE_AGG_SUM_DISC_TAX_I64: {
-                        __int128 x = (__int128)val(g.proj_a, row) * (g.one - val(g.proj_b, row))
-                                     * (g.one + val(g.proj_c, row));
-                        p2.lo = (int64_t)(uint64_t)x; p2.hi = (int64_t)(x >> 64); break;
-                    }
-                    default: p2.valid = false; break;
-                }
-                acc_apply_atomic(&scells[slot * n_aggs_ct + a], g.kind, p2);
-            }
-        }
-        __syncthreads();     /* LDS decode regions reused next tile */
-    }
-
-    /* flush the block table */
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t *bk = keys_out + (size_t)blockIdx.x * FUSEG_SLOTS;
-        AccCell *bc = cells_out + (size_t)blockIdx.x * FUSEG_SLOTS * n_aggs_ct;
-        for (uint32_t s2 = 0; s2 < FUSEG_SLOTS; s2++) {
-            bk[s2] = skeys[s2] < 0 ? 0xFFFFFFFFu : (uint32_t)skeys[s2];
-            for (uint32_t a = 0; a < n_aggs_ct; a++) {
-                const ThreadAcc &x = scells[s2 * n_aggs_ct + a];
-                AccCell cell{x.lo, x.hi, x.f, x.cnt};
-                bc[(size_t)s2 * n_aggs_ct + a] = cell;
-            }
-        }
     }
 }
 
@@ -3072,9 +2674,7 @@ void csgpu_release(cstripe_scan *s)
     if (g->d_tmp) HIP_DROP(hipFree(g->d_tmp));
     if (g->d_zsegs) HIP_DROP(hipFree(g->d_zsegs));
     if (g->d_zrtab) HIP_DROP(hipFree(g->d_zrtab));
-    if (g->d_segstart) HIP_DROP(hipFree(g->d_segstart));
     if (g->d_tiles) HIP_DROP(hipFree(g->d_tiles));
-    if (g->d_tiles2) HIP_DROP(hipFree(g->d_tiles2));
     if (g->d_error) HIP_DROP(hipFree(g->d_error));
     if (g->d_sel_mask) HIP_DROP(hipFree(g->d_sel_mask));
     if (g->d_sel_counts) HIP_DROP(hipFree(g->d_sel_counts));
@@ -3239,11 +2839,6 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         n_tiles_max += (r->stripes[sc.stripe].group_rows[sc.chunk] + 2047) / 2048;
     uint64_t max_blocks = (uint64_t)g->n_groups * tiles_pg;
     if (n_tiles_max > max_blocks) max_blocks = n_tiles_max;
-    {   /* lds_agg_kernel tiles every chunk at the full 2048-row pitch */
-        uint64_t b2 = (uint64_t)g->n_groups *
-                      ((r->head.chunk_row_limit + 2047) / 2048);
-        if (b2 > max_blocks) max_blocks = b2;
-    }
     g->max_blocks = (uint32_t)max_blocks;
 
     HIP_TRY(hipStreamCreate(&g->stream));
@@ -3281,8 +2876,6 @@ int csgpu_stage(cstripe_scan *s, int device_id)
     std::vector<SegDesc> h_zsegs;
     h_zsegs.reserve(n_zsegs);
     std::vector<uint32_t> seg_start((uint64_t)g->n_groups * n_proj, 0);
-    std::vector<uint8_t> col_g256(n_proj, 1);   /* stays 1 if every chunk is
-                                                 * dense uniform-256B lz4 */
     g->col_scratch.assign(n_proj, 0);
     if (n_proj > 4) g->fusable = false;
     std::vector<GroupDesc> h_groups(g->n_groups);
@@ -3341,35 +2934,18 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 cl.val_off = spos;
                 spos += align_up((uint64_t)nd.n.n_present * 4, 16);
                 g->fusable = false;
-                g->fusable_mixed = false;
-                g->all_canonP = false;
-                col_g256[pj] = 0;
                 h_colloc[(uint64_t)gi * n_proj + pj] = cl;
                 continue;
             }
-            {
-                const cs_skipnode &nd2 = st.nodes[c][sc.chunk];
-                const bool cp = nd2.n.comp_type == CSTRIPE_COMP_LZ4 &&
-                                nd2.n.n_segs == 1 &&
-                                (nd2.seg_modes[0] == CSF_SEGMODE_CONST ||
-                                 (nd2.seg_modes[0] > CSF_SEGMODE_P_BASE &&
-                                  nd2.seg_modes[0] <= CSF_SEGMODE_P_BASE + 4));
-                if (!cp || !(cl.flags & 2)) g->all_canonP = false;
-            }
-
             const bool canon = cs_node_canon(nd);
             if (canon || !(cl.flags & 2) || cl.type != CSTRIPE_I64 ||
                 nd.n.comp_type != CSTRIPE_COMP_LZ4)
                 g->fusable = false;
-            if (canon || !(cl.flags & 2) || (cl.width != 8 && cl.width != 1) ||
-                nd.n.comp_type != CSTRIPE_COMP_LZ4)
-                g->fusable_mixed = false;
             bool zr_dev = !canon && nd.n.comp_type == CSTRIPE_COMP_ZSTD;
             if (zr_dev)
                 for (uint8_t m : nd.seg_modes)
                     if (m != CSF_SEGMODE_ZR) { zr_dev = false; break; }
             if (zr_dev) {
-                col_g256[pj] = 0;
                 g->col_scratch[pj] = 1;
                 dpos = align_up(dpos, 16);
                 memcpy(h_data.data() + dpos, stripe_base + nd.n.value_off, nd.n.value_len);
@@ -3390,7 +2966,6 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 dpos += align_up(nd.n.value_len, 16);
                 spos += align_up(nd.n.decompressed_size, 16);
             } else if (canon) {
-                col_g256[pj] = 0;
                 /* stage the compressed stream; kernels read values straight
                  * out of it (col_value canonical path) */
                 dpos = align_up(dpos, 16);
@@ -3436,21 +3011,18 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 g->scratch_off[(uint64_t)gi * n_proj + pj] = spos;
                 seg_start[(uint64_t)gi * n_proj + pj] = (uint32_t)h_segs.size();
                 g->col_scratch[pj] = 1;
-                if (!(cl.flags & 2)) col_g256[pj] = 0;
                 uint32_t segi = 0;
                 const auto &seglist = st.nodes[c][sc.chunk].segs;
                 for (const csf_seg &sg : seglist) {
                     /* non-final segments exactly 256 B, final <= 256 B: the
-                     * fused kernels map row -> lane region as byteoff>>8 and
-                     * count tile segments as ceil(bytes/256), so an absorbed
+                     * fused kernel maps row -> lane region as byteoff>>8 and
+                     * counts tile segments as ceil(bytes/256), so an absorbed
                      * 257-271 B final segment would read the wrong region
                      * and overrun the segment list (round-1 advisor) */
                     if (sg.decomp_off != segi * 256u ||
                         (segi + 1 < seglist.size() ? sg.decomp_len != 256
                                                    : sg.decomp_len > 256)) {
                         g->fusable = false;
-                        g->fusable_mixed = false;
-                        col_g256[pj] = 0;
                     }
                     segi++;
                 }
@@ -3468,14 +3040,12 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 dpos += align_up(nd.n.value_len, 16);
                 spos += align_up(nd.n.decompressed_size, 16);
             } else if (nd.n.comp_type == CSTRIPE_COMP_NONE) {
-                col_g256[pj] = 0;
                 dpos = align_up(dpos, 16);
                 cl.val_off = dpos;
                 memcpy(h_data.data() + dpos, stripe_base + nd.n.value_off, nd.n.value_len);
                 dpos += align_up(nd.n.value_len, 16);
             } else if (nd.n.comp_type == CSTRIPE_COMP_ZSTD ||
                        nd.n.comp_type == CSTRIPE_COMP_PGLZ) {
-                col_g256[pj] = 0;
                 /* host-decode at stage (zstd: documented fallback, GPU zstd
                  * is a later item — SURVEY.md §8f(1); pglz is host-only by
                  * design: reference-migrated tables read correctly) */
@@ -3567,51 +3137,6 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         HIP_TRY(hipMemcpyAsync(g->d_tiles, h_tiles.data(),
                                h_tiles.size() * sizeof(FusedTile),
                                hipMemcpyHostToDevice, g->stream));
-    }
-    /* mixed-width (fused grouped) tiles: lane ranges by prefix */
-    if (g->fusable_mixed && g->n_groups > 0 && n_proj <= 8) {
-        uint32_t lb = 0;
-        for (uint32_t pj = 0; pj < n_proj; pj++) {
-            /* width from any group's colloc (uniform per column) */
-            uint8_t w = h_colloc[pj].width;   /* uniform per column */
-            g->fwidth[pj] = w;
-            g->flane_base[pj] = (uint16_t)lb;
-            lb += (uint32_t)FUSEG_TILE_ROWS * w / 256;
-        }
-        if (lb <= AGG_BLOCK) {
-            g->flanes_total = (uint16_t)lb;
-            std::vector<FusedTileG> h_tiles2;
-            for (uint32_t gi = 0; gi < g->n_groups; gi++) {
-                const cs_selchunk &sc = s->sel[gi];
-                uint32_t rows = r->stripes[sc.stripe].group_rows[sc.chunk];
-                uint32_t ntile = (rows + FUSEG_TILE_ROWS - 1) / FUSEG_TILE_ROWS;
-                for (uint32_t k = 0; k < ntile; k++) {
-                    FusedTileG ft{};
-                    ft.row_count = (k + 1 < ntile) ? FUSEG_TILE_ROWS
-                                                   : rows - k * FUSEG_TILE_ROWS;
-                    for (uint32_t pj = 0; pj < n_proj; pj++)
-                        ft.seg_base[pj] = seg_start[(uint64_t)gi * n_proj + pj]
-                                          + k * ((uint32_t)FUSEG_TILE_ROWS * g->fwidth[pj] / 256);
-                    h_tiles2.push_back(ft);
-                }
-            }
-            g->n_tiles2 = (uint32_t)h_tiles2.size();
-            HIP_TRY(hipMalloc(&g->d_tiles2, h_tiles2.size() * sizeof(FusedTileG)));
-            HIP_TRY(hipMemcpyAsync(g->d_tiles2, h_tiles2.data(),
-                                   h_tiles2.size() * sizeof(FusedTileG),
-                                   hipMemcpyHostToDevice, g->stream));
-        } else {
-            g->fusable_mixed = false;
-        }
-    }
-    g->greedy256_mask = 0;
-    for (uint32_t pj = 0; pj < n_proj; pj++)
-        if (col_g256[pj]) g->greedy256_mask |= 1ull << pj;
-    if (g->n_groups > 0 && n_proj > 0) {
-        HIP_TRY(hipMalloc(&g->d_segstart, seg_start.size() * 4));
-        HIP_TRY(hipMemcpyAsync(g->d_segstart, seg_start.data(),
-                               seg_start.size() * 4, hipMemcpyHostToDevice,
-                               g->stream));
     }
     HIP_TRY(hipStreamSynchronize(g->stream));
     g->colloc_host = h_colloc;
@@ -4310,384 +3835,128 @@ static void fill_preds(const cstripe_scan *s, AggParams &p)
     }
 }
 
-/* =====================================================================
- * scan_agg
- * ===================================================================== */
-
-int csgpu_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
-              const uint32_t *group_cols, uint32_t n_group_cols,
-              cstripe_group_result *gr, cstripe_partial *out)
+/* projected slot of a table column, -1 when out of range or not projected */
+static int proj_of(const cstripe_scan *s, int32_t col)
 {
-    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
-    cs_gpu_state *g = s->gpu;
-    cstripe_reader *r = s->r;
-    if (n_aggs > MAX_AGGS) { cs_set_err("too many aggs"); return CSTRIPE_ERR_ARG; }
-    if (s->preds.size() > MAX_PREDS) { cs_set_err("too many preds"); return CSTRIPE_ERR_ARG; }
+    if (col < 0 || col >= (int32_t)s->r->head.column_count) return -1;
+    return s->gpu->proj_of_col[col];
+}
 
-    AggParams p{};
-    p.n_preds = (uint32_t)s->preds.size();
+/* the AggParams header of scan_agg, its grouped form and scan_agg_hashed:
+ * tile geometry, predicates and the aggregates' projected operand slots */
+static int fill_agg_params(const cstripe_scan *s, const cstripe_agg_spec *aggs,
+                           uint32_t n_aggs, AggParams &p)
+{
+    const cs_gpu_state *g = s->gpu;
+    const cstripe_reader *r = s->r;
     p.n_aggs = n_aggs;
     p.n_proj = g->n_proj;
     p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
     if (p.tiles_per_group == 0) p.tiles_per_group = 1;
     p.n_groups = g->n_groups;
     fill_preds(s, p);
-    auto proj_of = [&](int32_t col) -> int {
-        if (col < 0 || col >= (int32_t)r->head.column_count) return -1;
-        return g->proj_of_col[col];
-    };
     for (uint32_t i = 0; i < n_aggs; i++) {
         p.aggs[i].kind = (uint8_t)aggs[i].kind;
         p.aggs[i].one = aggs[i].one;
-        int pa = proj_of(aggs[i].col_a), pb = proj_of(aggs[i].col_b), pc = proj_of(aggs[i].col_c);
+        int pa = proj_of(s, aggs[i].col_a), pb = proj_of(s, aggs[i].col_b), pc = proj_of(s, aggs[i].col_c);
         if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && pa < 0) { cs_set_err("agg %u: col_a not projected", i); return CSTRIPE_ERR_ARG; }
         if (agg_reads_vartext(r, aggs[i])) { cs_set_err("agg %u: a VARTEXT column can only be the operand of COUNT_COL", i); return CSTRIPE_ERR_ARG; }
         p.aggs[i].proj_a = (uint8_t)(pa < 0 ? 0 : pa);
         p.aggs[i].proj_b = (uint8_t)(pb < 0 ? 0 : pb);
         p.aggs[i].proj_c = (uint8_t)(pc < 0 ? 0 : pc);
     }
+    return CSTRIPE_OK;
+}
 
-    if (n_group_cols > 0) {
-        GroupParams gp{};
-        gp.base = p;
-        gp.n_group_cols = n_group_cols;
-        for (uint32_t i = 0; i < n_group_cols; i++) {
-            int pj = proj_of((int32_t)group_cols[i]);
-            if (pj < 0) { cs_set_err("group col %u not projected", group_cols[i]); return CSTRIPE_ERR_ARG; }
-            if (r->cols[group_cols[i]].type != CSTRIPE_I8 &&
-                r->cols[group_cols[i]].type != CSTRIPE_TEXT) { cs_set_err("group col %u must be I8 or TEXT", group_cols[i]); return CSTRIPE_ERR_ARG; }
-            gp.gproj[i] = (uint32_t)pj;
-        }
-        gp.n_work = g->n_groups * p.tiles_per_group;
-        if (gp.n_work == 0) {
-            gr->n_groups = 0;
-            s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
-            return CSTRIPE_OK;
-        }
-        const uint32_t n_waves = AGG_BLOCK / WAVE;
-        const uint32_t per_block = n_waves * GRP_SLOTS;
-        uint32_t grid = gp.n_work < GRP_GRID ? gp.n_work : GRP_GRID;
-        if (!g->d_gkeys) {
-            HIP_TRY(hipMalloc(&g->d_gkeys, (uint64_t)GRP_GRID * per_block * 4));
-            HIP_TRY(hipMalloc(&g->d_gcells, (uint64_t)GRP_GRID * per_block * MAX_AGGS * sizeof(AccCell)));
-            HIP_TRY(hipMalloc(&g->d_gfkeys, CSTRIPE_MAX_GROUPS * 4));
-            HIP_TRY(hipMalloc(&g->d_gfcells, (uint64_t)CSTRIPE_MAX_GROUPS * MAX_AGGS * sizeof(AccCell)));
-            HIP_TRY(hipMalloc(&g->d_gn, 4));
-        }
-        bool int_aggs_g = true;
-        for (uint32_t a = 0; a < n_aggs; a++)
-            if (aggs[a].kind == CSTRIPE_AGG_SUM_F64 || aggs[a].kind == CSTRIPE_AGG_MIN_F64 ||
-                aggs[a].kind == CSTRIPE_AGG_MAX_F64)
-                int_aggs_g = false;
-        if (g->all_dense) {
-            /* multi-row grouped kernel (windowed loads + per-wave 16-slot
-             * LDS tables); falls back below on >16 distinct keys (flag 8).
-             * Key columns stored as uniform 256 B greedy-LZ4 segments are
-             * decoded INSIDE the kernel (half-tile LDS staging) — when they
-             * are the only scratch consumers, the standalone decode kernel
-             * and its scratch round trip are skipped entirely. */
-            const uint32_t mg_per_block = n_waves * MGRP_SLOTS;
-            uint32_t mgrid = gp.n_work < GRP_GRID ? gp.n_work : GRP_GRID;
-            gp.kdec_mask = 0;
-            uint32_t extra_lds = 0;
-            /* fused in-kernel key decode measured SLOWER than the separate
-             * massively-parallel decode kernel (idle lanes during the
-             * half-tile decode phase + LDS-driven occupancy loss): keep it
-             * behind the variant knob for future work */
-            static const int gvar2 = [] {
-                const char *e = getenv("CSTRIPE_GROUPED_VARIANT");
-                return e ? atoi(e) : 0;
-            }();
-            for (uint32_t i = 0; i < n_group_cols; i++) {
-                const uint32_t pj = gp.gproj[i];
-                const uint32_t w = g->colloc_host[pj].width;
-                gp.kwidth[i] = w;
-                if (gvar2 == 2 && ((g->greedy256_mask >> pj) & 1)) {
-                    gp.kdec_mask |= 1u << i;
-                    extra_lds += ((2048u * w + 255u) / 256u) * 280u;
-                }
-            }
-            uint32_t mlds = (n_waves * MGRP_SLOTS * n_aggs *
-                             (uint32_t)sizeof(ThreadAcc) + 15u) & ~15u;
-            mlds += extra_lds;
-            bool need_decode = g->n_zsegs > 0;
-            for (uint32_t pj = 0; pj < g->n_proj && !need_decode; pj++) {
-                if (!g->col_scratch[pj]) continue;
-                bool fused_key = false;
-                for (uint32_t i = 0; i < n_group_cols; i++)
-                    fused_key |= gp.gproj[i] == pj && (gp.kdec_mask & (1u << i));
-                if (!fused_key) need_decode = true;
-            }
-            HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
-            HIP_TRY(hipEventRecord(g->ev0, g->stream));
-            if (need_decode) { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
-            HIP_TRY(hipEventRecord(g->ev1, g->stream));
-            auto launchmg = [&](auto *kern) {
-                hipLaunchKernelGGL(kern, dim3(mgrid), dim3(AGG_BLOCK), mlds, g->stream,
-                                   g->d_data, g->d_scratch, g->d_groups, g->d_colloc,
-                                   g->d_segs, g->d_segstart,
-                                   g->d_gkeys, g->d_gcells, g->d_error, gp);
-            };
-            static const int gvar = [] {
-                const char *e = getenv("CSTRIPE_GROUPED_VARIANT");
-                return e ? atoi(e) : 0;
-            }();
-            if (gvar == 1) {       /* forced 5 waves/SIMD A/B variant */
-                if (n_aggs == 5) launchmg(multi_grouped_kernel<5, 8, 5>);
-                else if (n_aggs == 1) launchmg(multi_grouped_kernel<1, 8, 5>);
-                else if (n_aggs == 2) launchmg(multi_grouped_kernel<2, 8, 5>);
-                else if (n_aggs == 4) launchmg(multi_grouped_kernel<4, 8, 5>);
-                else launchmg(multi_grouped_kernel<-1, 4>);
-            } else {
-                if (n_aggs == 5) launchmg(multi_grouped_kernel<5, 8>);
-                else if (n_aggs == 1) launchmg(multi_grouped_kernel<1, 8>);
-                else if (n_aggs == 2) launchmg(multi_grouped_kernel<2, 8>);
-                else if (n_aggs == 4) launchmg(multi_grouped_kernel<4, 8>);
-                else launchmg(multi_grouped_kernel<-1, 4>);
-            }
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(grouped_final_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
-                               g->d_gkeys, g->d_gcells, mgrid, mg_per_block,
-                               g->d_gfkeys, g->d_gfcells, g->d_gn, g->d_error, gp);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(g->ev2, g->stream));
-            int h_err = 0;
-            HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-            HIP_TRY(hipStreamSynchronize(g->stream));
-            if (h_err & 4) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
-            if (h_err == 0) {
-                s->last_fused = 0;   /* i8 key columns decode to scratch */
-                uint32_t h_keys[CSTRIPE_MAX_GROUPS];
-                std::vector<AccCell> h_cells((size_t)CSTRIPE_MAX_GROUPS * n_aggs);
-                uint32_t h_n = 0;
-                HIP_TRY(hipMemcpyAsync(h_keys, g->d_gfkeys, sizeof(h_keys), hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipMemcpyAsync(h_cells.data(), g->d_gfcells, h_cells.size() * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipMemcpyAsync(&h_n, g->d_gn, 4, hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipStreamSynchronize(g->stream));
-                float ms_d = 0, ms_k = 0;
-                (void)hipEventElapsedTime(&ms_d, g->ev0, g->ev1);
-                (void)hipEventElapsedTime(&ms_k, g->ev1, g->ev2);
-                s->last_decode_ms = ms_d;
-                s->last_agg_ms = ms_k;
-                s->last_kernel_ms = ms_d + ms_k;
-                std::vector<uint32_t> order(h_n);
-                for (uint32_t i = 0; i < h_n; i++) order[i] = i;
-                std::sort(order.begin(), order.end(),
-                          [&](uint32_t a, uint32_t b) { return h_keys[a] < h_keys[b]; });
-                gr->n_groups = h_n;
-                for (uint32_t oi = 0; oi < h_n; oi++) {
-                    uint32_t i = order[oi];
-                    gr->keys[oi] = h_keys[i];
-                    for (uint32_t a = 0; a < n_aggs; a++) {
-                        const AccCell &cc2 = h_cells[(size_t)i * n_aggs + a];
-                        cstripe_partial o{};
-                        o.count = cc2.cnt;
-                        o.is_null = (cc2.cnt == 0) ? 1 : 0;
-                        switch (aggs[a].kind) {
-                            case CSTRIPE_AGG_COUNT_STAR:
-                            case CSTRIPE_AGG_COUNT_COL:
-                                o.i128_lo = cc2.cnt; o.is_null = 0; break;
-                            case CSTRIPE_AGG_SUM_F64:
-                            case CSTRIPE_AGG_MIN_F64:
-                            case CSTRIPE_AGG_MAX_F64:
-                                if (!o.is_null) o.f64 = cc2.f; break;
-                            case CSTRIPE_AGG_MIN_I64:
-                            case CSTRIPE_AGG_MAX_I64:
-                                if (!o.is_null) { o.i128_lo = cc2.lo; o.i128_hi = cc2.lo < 0 ? -1 : 0; }
-                                break;
-                            default:
-                                if (!o.is_null) { o.i128_lo = cc2.lo; o.i128_hi = cc2.hi; }
-                                break;
-                        }
-                        out[(size_t)oi * n_aggs + a] = o;
-                    }
-                }
-                return CSTRIPE_OK;
-            }
-            /* flag 8: >16 distinct keys — fall through to the 64-group path */
-        }
-        if (g->fusable_mixed && int_aggs_g && g->d_tiles2) {
-            /* fused grouped: decode tile to LDS + atomic group table; falls
-             * back below when >16 distinct groups (device flag 8) */
-            FusedGParams fgp{};
-            fgp.base = p;
-            fgp.n_group_cols = n_group_cols;
-            for (uint32_t i = 0; i < n_group_cols; i++) fgp.gproj[i] = gp.gproj[i];
-            fgp.n_tiles = g->n_tiles2;
-            for (uint32_t i = 0; i < 8; i++) { fgp.lane_base[i] = g->flane_base[i]; fgp.width[i] = g->fwidth[i]; }
-            fgp.lanes_total = g->flanes_total;
-            uint32_t fgrid = g->n_tiles2 < FUSEG_GRID ? g->n_tiles2 : FUSEG_GRID;
-            uint32_t flds = (uint32_t)fgp.lanes_total * FUSE_STRIDE + FUSEG_SLOTS * 4
-                            + FUSEG_SLOTS * n_aggs * (uint32_t)sizeof(ThreadAcc);
-            HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
-            HIP_TRY(hipEventRecord(g->ev0, g->stream));
-            auto launchfg = [&](auto *kern) {
-                hipLaunchKernelGGL(kern, dim3(fgrid), dim3(AGG_BLOCK), flds, g->stream,
-                                   g->d_data, g->d_segs, g->d_tiles2, g->d_gkeys,
-                                   g->d_gcells, g->d_error, fgp);
-            };
-            if (n_aggs == 5) launchfg(fused_grouped_kernel<5>);
-            else if (n_aggs == 1) launchfg(fused_grouped_kernel<1>);
-            else if (n_aggs == 2) launchfg(fused_grouped_kernel<2>);
-            else launchfg(fused_grouped_kernel<-1>);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(g->ev1, g->stream));
-            hipLaunchKernelGGL(grouped_final_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
-                               g->d_gkeys, g->d_gcells, fgrid, FUSEG_SLOTS,
-                               g->d_gfkeys, g->d_gfcells, g->d_gn, g->d_error, gp);
-        HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(g->ev2, g->stream));
-            int h_err = 0;
-            HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-            HIP_TRY(hipStreamSynchronize(g->stream));
-            if (h_err & 4) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
-            if (h_err == 0) {
-                s->last_fused = 1;
-                uint32_t h_keys[CSTRIPE_MAX_GROUPS];
-                std::vector<AccCell> h_cells((size_t)CSTRIPE_MAX_GROUPS * n_aggs);
-                uint32_t h_n = 0;
-                HIP_TRY(hipMemcpyAsync(h_keys, g->d_gfkeys, sizeof(h_keys), hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipMemcpyAsync(h_cells.data(), g->d_gfcells, h_cells.size() * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipMemcpyAsync(&h_n, g->d_gn, 4, hipMemcpyDeviceToHost, g->stream));
-                HIP_TRY(hipStreamSynchronize(g->stream));
-                float ms_f = 0, ms_r = 0;
-                (void)hipEventElapsedTime(&ms_f, g->ev0, g->ev1);
-                (void)hipEventElapsedTime(&ms_r, g->ev1, g->ev2);
-                s->last_decode_ms = ms_f;
-                s->last_agg_ms = ms_r;
-                s->last_kernel_ms = ms_f + ms_r;
-                std::vector<uint32_t> order(h_n);
-                for (uint32_t i = 0; i < h_n; i++) order[i] = i;
-                std::sort(order.begin(), order.end(),
-                          [&](uint32_t a, uint32_t b) { return h_keys[a] < h_keys[b]; });
-                gr->n_groups = h_n;
-                for (uint32_t oi = 0; oi < h_n; oi++) {
-                    uint32_t i = order[oi];
-                    gr->keys[oi] = h_keys[i];
-                    for (uint32_t a = 0; a < n_aggs; a++) {
-                        const AccCell &cc2 = h_cells[(size_t)i * n_aggs + a];
-                        cstripe_partial o{};
-                        o.count = cc2.cnt;
-                        o.is_null = (cc2.cnt == 0) ? 1 : 0;
-                        switch (aggs[a].kind) {
-                            case CSTRIPE_AGG_COUNT_STAR:
-                            case CSTRIPE_AGG_COUNT_COL:
-                                o.i128_lo = cc2.cnt; o.is_null = 0; break;
-                            case CSTRIPE_AGG_MIN_I64:
-                            case CSTRIPE_AGG_MAX_I64:
-                                if (!o.is_null) { o.i128_lo = cc2.lo; o.i128_hi = cc2.lo < 0 ? -1 : 0; }
-                                break;
-                            default:
-                                if (!o.is_null) { o.i128_lo = cc2.lo; o.i128_hi = cc2.hi; }
-                                break;
-                        }
-                        out[(size_t)oi * n_aggs + a] = o;
-                    }
-                }
-                return CSTRIPE_OK;
-            }
-        }
+static bool aggs_all_integer(const cstripe_agg_spec *aggs, uint32_t n_aggs)
+{
+    for (uint32_t a = 0; a < n_aggs; a++)
+        if (aggs[a].kind == CSTRIPE_AGG_SUM_F64 || aggs[a].kind == CSTRIPE_AGG_MIN_F64 ||
+            aggs[a].kind == CSTRIPE_AGG_MAX_F64)
+            return false;
+    return true;
+}
 
-        uint32_t lds = n_waves * GRP_SLOTS * 4 + n_waves * GRP_SLOTS * n_aggs * (uint32_t)sizeof(ThreadAcc);
-        HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
-        HIP_TRY(hipEventRecord(g->ev0, g->stream));
-        { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
-        HIP_TRY(hipEventRecord(g->ev1, g->stream));
-        {
-            auto launchg = [&](auto *kern) {
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(AGG_BLOCK), lds, g->stream,
-                                   g->d_data, g->d_scratch, g->d_rank, g->d_groups,
-                                   g->d_colloc, g->d_gkeys, g->d_gcells, g->d_error, gp);
-            };
-            if (n_aggs == 5) launchg(grouped_agg_kernel<5>);
-            else if (n_aggs == 1) launchg(grouped_agg_kernel<1>);
-            else if (n_aggs == 2) launchg(grouped_agg_kernel<2>);
-            else launchg(grouped_agg_kernel<-1>);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(grouped_final_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
-                           g->d_gkeys, g->d_gcells, grid, per_block,
-                           g->d_gfkeys, g->d_gfcells, g->d_gn, g->d_error, gp);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(g->ev2, g->stream));
-
-        uint32_t h_keys[CSTRIPE_MAX_GROUPS];
-        std::vector<AccCell> h_cells((size_t)CSTRIPE_MAX_GROUPS * n_aggs);
-        uint32_t h_n = 0;
-        int h_err = 0;
-        HIP_TRY(hipMemcpyAsync(h_keys, g->d_gfkeys, sizeof(h_keys), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipMemcpyAsync(h_cells.data(), g->d_gfcells, h_cells.size() * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipMemcpyAsync(&h_n, g->d_gn, 4, hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (h_err & 4) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
-        if (h_err) { cs_set_err("too many distinct groups (device flag %d; caps: %d/wave, %d total)", h_err, GRP_SLOTS, CSTRIPE_MAX_GROUPS); return CSTRIPE_ERR; }
-
-        float ms_decode = 0, ms_agg = 0;
-        (void)hipEventElapsedTime(&ms_decode, g->ev0, g->ev1);
-        (void)hipEventElapsedTime(&ms_agg, g->ev1, g->ev2);
-        s->last_decode_ms = ms_decode;
-        s->last_agg_ms = ms_agg;
-        s->last_kernel_ms = ms_decode + ms_agg;
-
-        /* sort groups by key for deterministic output (oracle does the same) */
-        std::vector<uint32_t> order(h_n);
-        for (uint32_t i = 0; i < h_n; i++) order[i] = i;
-        std::sort(order.begin(), order.end(),
-                  [&](uint32_t a, uint32_t b) { return h_keys[a] < h_keys[b]; });
-        gr->n_groups = h_n;
-        for (uint32_t oi = 0; oi < h_n; oi++) {
-            uint32_t i = order[oi];
-            gr->keys[oi] = h_keys[i];
-            for (uint32_t a = 0; a < n_aggs; a++) {
-                const AccCell &c = h_cells[(size_t)i * n_aggs + a];
-                cstripe_partial o{};
-                o.count = c.cnt;
-                o.is_null = (c.cnt == 0) ? 1 : 0;
-                switch (aggs[a].kind) {
-                    case CSTRIPE_AGG_COUNT_STAR:
-                    case CSTRIPE_AGG_COUNT_COL:
-                        o.i128_lo = c.cnt; o.is_null = 0; break;
-                    case CSTRIPE_AGG_SUM_F64:
-                    case CSTRIPE_AGG_MIN_F64:
-                    case CSTRIPE_AGG_MAX_F64:
-                        if (!o.is_null) o.f64 = c.f; break;
-                    case CSTRIPE_AGG_MIN_I64:
-                    case CSTRIPE_AGG_MAX_I64:
-                        if (!o.is_null) { o.i128_lo = c.lo; o.i128_hi = c.lo < 0 ? -1 : 0; } break;
-                    default:
-                        if (!o.is_null) { o.i128_lo = c.lo; o.i128_hi = c.hi; } break;
-                }
-                out[(size_t)oi * n_aggs + a] = o;
-            }
-        }
-        return CSTRIPE_OK;
+/* device accumulator cell -> wire partial: COUNT kinds are never NULL, every
+ * other kind is NULL (value fields zero) iff no row contributed */
+static cstripe_partial cell_to_partial(uint32_t kind, const AccCell &c)
+{
+    cstripe_partial o{};
+    o.count = c.cnt;
+    if (kind == CSTRIPE_AGG_COUNT_STAR || kind == CSTRIPE_AGG_COUNT_COL) {
+        o.i128_lo = c.cnt;
+        return o;
     }
+    o.is_null = (c.cnt == 0) ? 1 : 0;
+    if (o.is_null) return o;
+    switch (kind) {
+        case CSTRIPE_AGG_SUM_F64:
+        case CSTRIPE_AGG_MIN_F64:
+        case CSTRIPE_AGG_MAX_F64:
+            o.f64 = c.f; break;
+        case CSTRIPE_AGG_MIN_I64:
+        case CSTRIPE_AGG_MAX_I64:
+            o.i128_lo = c.lo; o.i128_hi = c.lo < 0 ? -1 : 0; break;
+        default:
+            o.i128_lo = c.lo; o.i128_hi = c.hi; break;
+    }
+    return o;
+}
 
-    uint32_t n_blocks = g->n_groups * p.tiles_per_group;
+/* =====================================================================
+ * scan_agg
+ * ===================================================================== */
+
+/* ev0..ev1 is the first stage (decode, or the fused kernel), ev1..ev2 the
+ * aggregate; the stream must be synchronised past ev2 */
+static void record_stage_ms(cstripe_scan *s)
+{
+    const cs_gpu_state *g = s->gpu;
+    float ms_first = 0, ms_agg = 0;
+    (void)hipEventElapsedTime(&ms_first, g->ev0, g->ev1);
+    (void)hipEventElapsedTime(&ms_agg, g->ev1, g->ev2);
+    s->last_decode_ms = ms_first;
+    s->last_agg_ms = ms_agg;
+    s->last_kernel_ms = ms_first + ms_agg;
+}
+
+/* ungrouped: d_final and the device flags -> out[n_aggs]; any flag is a
+ * decode error here */
+static int collect_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
+                             uint32_t n_aggs, cstripe_partial *out)
+{
+    cs_gpu_state *g = s->gpu;
+    AccCell h_final[MAX_AGGS];
+    int h_err = 0;
+    HIP_TRY(hipMemcpyAsync(h_final, g->d_final, n_aggs * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    record_stage_ms(s);
+    for (uint32_t a = 0; a < n_aggs; a++)
+        out[a] = cell_to_partial(aggs[a].kind, h_final[a]);
+    return CSTRIPE_OK;
+}
+
+static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
+                         uint32_t n_aggs, const AggParams &p, cstripe_partial *out)
+{
+    cs_gpu_state *g = s->gpu;
+    const uint32_t n_blocks = g->n_groups * p.tiles_per_group;
     if (n_blocks == 0) {
         /* empty selection — all-NULL partials (combine applies COUNT coalesce) */
-        for (uint32_t a = 0; a < n_aggs; a++) {
-            cstripe_partial z{};
-            z.is_null = 1;
-            if (aggs[a].kind == CSTRIPE_AGG_COUNT_STAR || aggs[a].kind == CSTRIPE_AGG_COUNT_COL) z.is_null = 0;
-            out[a] = z;
-        }
+        for (uint32_t a = 0; a < n_aggs; a++)
+            out[a] = cell_to_partial(aggs[a].kind, AccCell{});
         s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
         return CSTRIPE_OK;
     }
 
-    bool int_aggs = true;
-    for (uint32_t a = 0; a < n_aggs; a++)
-        if (aggs[a].kind == CSTRIPE_AGG_SUM_F64 || aggs[a].kind == CSTRIPE_AGG_MIN_F64 ||
-            aggs[a].kind == CSTRIPE_AGG_MAX_F64)
-            int_aggs = false;
-
     HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
-    if (g->fusable && int_aggs && g->d_tiles) {
-        /* fused decode+filter+aggregate: no scratch round trip */
+    HIP_TRY(hipEventRecord(g->ev0, g->stream));
+    if (g->fusable && aggs_all_integer(aggs, n_aggs) && g->d_tiles) {
+        /* fused decode+filter+aggregate: no scratch round trip; the first
+         * stage time is the fused kernel (decode dominates) */
         s->last_fused = 1;
-        HIP_TRY(hipEventRecord(g->ev0, g->stream));
         auto launchf = [&](auto *kern) {
             hipLaunchKernelGGL(kern, dim3(g->n_tiles), dim3(AGG_BLOCK),
                                AGG_BLOCK * FUSE_STRIDE, g->stream,
@@ -4703,195 +3972,189 @@ int csgpu_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(g->ev1, g->stream));
         { int _rc = launch_final_reduce(g, g->n_tiles, p); if (_rc != CSTRIPE_OK) return _rc; }
-        HIP_TRY(hipEventRecord(g->ev2, g->stream));
-
-        AccCell h_final[MAX_AGGS];
-        int h_err = 0;
-        HIP_TRY(hipMemcpyAsync(h_final, g->d_final, n_aggs * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
-
-        float ms_fused = 0, ms_red = 0;
-        (void)hipEventElapsedTime(&ms_fused, g->ev0, g->ev1);
-        (void)hipEventElapsedTime(&ms_red, g->ev1, g->ev2);
-        s->last_decode_ms = ms_fused;     /* the fused kernel (decode dominates) */
-        s->last_agg_ms = ms_red;
-        s->last_kernel_ms = ms_fused + ms_red;
-
-        for (uint32_t a = 0; a < n_aggs; a++) {
-            cstripe_partial o{};
-            const AccCell &cc = h_final[a];
-            o.count = cc.cnt;
-            o.is_null = (cc.cnt == 0) ? 1 : 0;
-            if (o.is_null && aggs[a].kind != CSTRIPE_AGG_COUNT_STAR &&
-                aggs[a].kind != CSTRIPE_AGG_COUNT_COL) { out[a] = o; continue; }
-            switch (aggs[a].kind) {
-                case CSTRIPE_AGG_COUNT_STAR:
-                case CSTRIPE_AGG_COUNT_COL:
-                    o.i128_lo = cc.cnt; o.is_null = 0; break;
-                case CSTRIPE_AGG_MIN_I64:
-                case CSTRIPE_AGG_MAX_I64:
-                    o.i128_lo = cc.lo; o.i128_hi = cc.lo < 0 ? -1 : 0; break;
-                default:
-                    o.i128_lo = cc.lo; o.i128_hi = cc.hi; break;
-            }
-            out[a] = o;
-        }
-        return CSTRIPE_OK;
-    }
-
-    s->last_fused = 0;
-    HIP_TRY(hipEventRecord(g->ev0, g->stream));
-    { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
-    HIP_TRY(hipEventRecord(g->ev1, g->stream));
-    if (g->all_dense) {
-        /* all-dense: paired-row kernel — one wide load per column covers
-         * two rows (canonical closed-form or decoded/raw typed arrays) */
-        auto launchp = [&](auto *kern) {
-            hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(AGG_BLOCK), 0, g->stream,
-                               g->d_data, g->d_scratch, g->d_groups,
-                               g->d_colloc, g->d_block, p);
-        };
-        /* variant knob for on-hardware A/B (default = R8, natural occupancy) */
-        static const int kvar = [] {
-            const char *e = getenv("CSTRIPE_KERNEL_VARIANT");
-            return e ? atoi(e) : 1;     /* measured best: R8 + 8 waves/SIMD */
-        }();
-        if (kvar == 3 && g->all_canonP) {
-            /* experimental LDS-staged scan: bulk-load pred streams to LDS */
-            uint32_t tiles2 = (r->head.chunk_row_limit + LDSK_TILE - 1) / LDSK_TILE;
-            if (tiles2 == 0) tiles2 = 1;
-            const uint32_t nb2 = g->n_groups * tiles2;
-            uint32_t lds_need = 0;
-            bool lds_ok = true;
-            {
-                bool seen[MAX_PROJ] = {};
-                for (uint32_t i = 0; i < p.n_preds; i++) {
-                    const uint32_t pj = p.preds[i].proj;
-                    if (seen[pj]) continue;
-                    seen[pj] = true;
-                    uint32_t maxstep = 0;
-                    for (uint32_t gi = 0; gi < g->n_groups; gi++) {
-                        const ColLoc &cl = g->colloc_host[(uint64_t)gi * g->n_proj + pj];
-                        if (cl.mode != CSF_SEGMODE_CONST)
-                            maxstep = max(maxstep, (uint32_t)cl.L + 3u);
-                    }
-                    lds_need += LDSK_TILE * maxstep + 64;
-                }
-                if (lds_need > 100 * 1024 || p.n_preds == 0) lds_ok = false;
-            }
-            if (lds_ok) {
-                auto launchl = [&](auto *kern) {
-                    hipLaunchKernelGGL(kern, dim3(nb2), dim3(AGG_BLOCK), lds_need,
-                                       g->stream, g->d_data, g->d_scratch,
-                                       g->d_groups, g->d_colloc, g->d_block,
-                                       tiles2, p);
-                };
-                if (p.n_preds == 5 && n_aggs == 2) launchl(lds_agg_kernel<5, 2>);
-                else if (p.n_preds == 5 && n_aggs == 1) launchl(lds_agg_kernel<5, 1>);
-                else if (p.n_preds == 1 && n_aggs == 1) launchl(lds_agg_kernel<1, 1>);
-                else launchl(lds_agg_kernel<-1, -1>);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(g->ev1, g->stream));
-                { int _rc = launch_final_reduce(g, nb2, p); if (_rc != CSTRIPE_OK) return _rc; }
-                HIP_TRY(hipEventRecord(g->ev2, g->stream));
-                goto collect_ungrouped;
-            }
-        }
-        if (kvar == 1) {        /* forced 8 waves/SIMD (64 VGPRs, some spill) */
+    } else {
+        s->last_fused = 0;
+        { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+        HIP_TRY(hipEventRecord(g->ev1, g->stream));
+        if (g->all_dense) {
+            /* all-dense: R-row windowed kernel (canonical closed-form or
+             * decoded/raw typed arrays); hot shapes run R8 at a forced
+             * 8 waves/SIMD, measured best */
+            auto launchp = [&](auto *kern) {
+                hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(AGG_BLOCK), 0, g->stream,
+                                   g->d_data, g->d_scratch, g->d_groups,
+                                   g->d_colloc, g->d_block, p);
+            };
             if (p.n_preds == 5 && n_aggs == 2) launchp(multi_agg_kernel<5, 2, 8, 8>);
             else if (p.n_preds == 5 && n_aggs == 1) launchp(multi_agg_kernel<5, 1, 8, 8>);
             else if (p.n_preds == 1 && n_aggs == 1) launchp(multi_agg_kernel<1, 1, 8, 8>);
             else if (p.n_preds == 2 && n_aggs == 2) launchp(multi_agg_kernel<2, 2, 8, 8>);
             else if (p.n_preds == 5 && n_aggs == 4) launchp(multi_agg_kernel<5, 4, 8, 8>);
             else launchp(multi_agg_kernel<-1, -1, 4>);
-        } else if (kvar == 4) { /* R8 + 7 waves/SIMD */
-            if (p.n_preds == 5 && n_aggs == 2) launchp(multi_agg_kernel<5, 2, 8, 7>);
-            else if (p.n_preds == 5 && n_aggs == 1) launchp(multi_agg_kernel<5, 1, 8, 7>);
-            else if (p.n_preds == 1 && n_aggs == 1) launchp(multi_agg_kernel<1, 1, 8, 7>);
-            else launchp(multi_agg_kernel<-1, -1, 4>);
-        } else if (kvar == 2) { /* R=4 */
-            if (p.n_preds == 5 && n_aggs == 2) launchp(multi_agg_kernel<5, 2, 4>);
-            else if (p.n_preds == 5 && n_aggs == 1) launchp(multi_agg_kernel<5, 1, 4>);
-            else if (p.n_preds == 1 && n_aggs == 1) launchp(multi_agg_kernel<1, 1, 4>);
-            else if (p.n_preds == 2 && n_aggs == 2) launchp(multi_agg_kernel<2, 2, 4>);
-            else if (p.n_preds == 5 && n_aggs == 4) launchp(multi_agg_kernel<5, 4, 4>);
-            else launchp(multi_agg_kernel<-1, -1, 4>);
         } else {
-            if (p.n_preds == 5 && n_aggs == 2) launchp(multi_agg_kernel<5, 2, 8>);
-            else if (p.n_preds == 5 && n_aggs == 1) launchp(multi_agg_kernel<5, 1, 8>);
-            else if (p.n_preds == 1 && n_aggs == 1) launchp(multi_agg_kernel<1, 1, 8>);
-            else if (p.n_preds == 2 && n_aggs == 2) launchp(multi_agg_kernel<2, 2, 8>);
-            else if (p.n_preds == 5 && n_aggs == 4) launchp(multi_agg_kernel<5, 4, 8>);
-            else launchp(multi_agg_kernel<-1, -1, 4>);
+            auto launch = [&](auto *kern) {
+                hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(AGG_BLOCK), 0, g->stream,
+                                   g->d_data, g->d_scratch, g->d_rank, g->d_groups,
+                                   g->d_colloc, g->d_block, p);
+            };
+            /* hot shapes compiled with unrolled pred/agg loops */
+            if (p.n_preds == 5 && n_aggs == 2) launch(filter_agg_kernel<5, 2>);
+            else if (p.n_preds == 5 && n_aggs == 1) launch(filter_agg_kernel<5, 1>);
+            else if (p.n_preds == 1 && n_aggs == 1) launch(filter_agg_kernel<1, 1>);
+            else if (p.n_preds == 2 && n_aggs == 2) launch(filter_agg_kernel<2, 2>);
+            else launch(filter_agg_kernel<-1, -1>);
         }
         HIP_TRY(hipGetLastError());
-    } else {
-        auto launch = [&](auto *kern) {
-            hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(AGG_BLOCK), 0, g->stream,
-                               g->d_data, g->d_scratch, g->d_rank, g->d_groups,
-                               g->d_colloc, g->d_block, p);
-        };
-        /* hot shapes compiled with unrolled pred/agg loops */
-        if (p.n_preds == 5 && n_aggs == 2) launch(filter_agg_kernel<5, 2>);
-        else if (p.n_preds == 5 && n_aggs == 1) launch(filter_agg_kernel<5, 1>);
-        else if (p.n_preds == 1 && n_aggs == 1) launch(filter_agg_kernel<1, 1>);
-        else if (p.n_preds == 2 && n_aggs == 2) launch(filter_agg_kernel<2, 2>);
-        else launch(filter_agg_kernel<-1, -1>);
-        HIP_TRY(hipGetLastError());
+        { int _rc = launch_final_reduce(g, n_blocks, p); if (_rc != CSTRIPE_OK) return _rc; }
     }
-    { int _rc = launch_final_reduce(g, n_blocks, p); if (_rc != CSTRIPE_OK) return _rc; }
     HIP_TRY(hipEventRecord(g->ev2, g->stream));
+    return collect_ungrouped(s, aggs, n_aggs, out);
+}
 
-collect_ungrouped:
-    ;
-    AccCell h_final[MAX_AGGS];
-    int h_err = 0;
-    HIP_TRY(hipMemcpyAsync(h_final, g->d_final, n_aggs * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+/* grouped: merge the per-block tables just written (grouped_final_kernel),
+ * close the timing window and read the device flags back */
+static int grouped_merge(cs_gpu_state *g, const GroupParams &gp, uint32_t grid,
+                         uint32_t per_block, int *h_err)
+{
+    hipLaunchKernelGGL(grouped_final_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_gkeys, g->d_gcells, grid, per_block,
+                       g->d_gfkeys, g->d_gfcells, g->d_gn, g->d_error, gp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->ev2, g->stream));
+    HIP_TRY(hipMemcpyAsync(h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    return CSTRIPE_OK;
+}
 
-    float ms_decode = 0, ms_agg = 0;
-    (void)hipEventElapsedTime(&ms_decode, g->ev0, g->ev1);
-    (void)hipEventElapsedTime(&ms_agg, g->ev1, g->ev2);
-    s->last_decode_ms = ms_decode;
-    s->last_agg_ms = ms_agg;
-    s->last_kernel_ms = ms_decode + ms_agg;
-
-    for (uint32_t a = 0; a < n_aggs; a++) {
-        cstripe_partial o{};
-        const AccCell &c = h_final[a];
-        o.count = c.cnt;
-        o.is_null = (c.cnt == 0) ? 1 : 0;
-        if (o.is_null && aggs[a].kind != CSTRIPE_AGG_COUNT_STAR &&
-            aggs[a].kind != CSTRIPE_AGG_COUNT_COL) { out[a] = o; continue; }
-        switch (aggs[a].kind) {
-            case CSTRIPE_AGG_COUNT_STAR:
-            case CSTRIPE_AGG_COUNT_COL:
-                o.count = c.cnt;
-                o.i128_lo = c.cnt;
-                o.is_null = 0;
-                break;
-            case CSTRIPE_AGG_SUM_F64:
-            case CSTRIPE_AGG_MIN_F64:
-            case CSTRIPE_AGG_MAX_F64:
-                o.f64 = c.f;
-                break;
-            case CSTRIPE_AGG_MIN_I64:
-            case CSTRIPE_AGG_MAX_I64:
-                o.i128_lo = c.lo;
-                o.i128_hi = c.lo < 0 ? -1 : 0;
-                break;
-            default:
-                o.i128_lo = c.lo;
-                o.i128_hi = c.hi;
-                break;
-        }
-        out[a] = o;
+/* grouped: the merged keys, cells and count -> gr and out, sorted by key for
+ * deterministic output (the oracle does the same) */
+static int collect_grouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
+                           uint32_t n_aggs, cstripe_group_result *gr,
+                           cstripe_partial *out)
+{
+    cs_gpu_state *g = s->gpu;
+    uint32_t h_keys[CSTRIPE_MAX_GROUPS];
+    std::vector<AccCell> h_cells((size_t)CSTRIPE_MAX_GROUPS * n_aggs);
+    uint32_t h_n = 0;
+    HIP_TRY(hipMemcpyAsync(h_keys, g->d_gfkeys, sizeof(h_keys), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(h_cells.data(), g->d_gfcells, h_cells.size() * sizeof(AccCell), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(&h_n, g->d_gn, 4, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    record_stage_ms(s);
+    s->last_fused = 0;   /* every grouped path decodes to scratch */
+    std::vector<uint32_t> order(h_n);
+    for (uint32_t i = 0; i < h_n; i++) order[i] = i;
+    std::sort(order.begin(), order.end(),
+              [&](uint32_t a, uint32_t b) { return h_keys[a] < h_keys[b]; });
+    gr->n_groups = h_n;
+    for (uint32_t oi = 0; oi < h_n; oi++) {
+        const uint32_t i = order[oi];
+        gr->keys[oi] = h_keys[i];
+        for (uint32_t a = 0; a < n_aggs; a++)
+            out[(size_t)oi * n_aggs + a] =
+                cell_to_partial(aggs[a].kind, h_cells[(size_t)i * n_aggs + a]);
     }
     return CSTRIPE_OK;
+}
+
+static int agg_grouped(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                       const uint32_t *group_cols, uint32_t n_group_cols,
+                       const AggParams &p, cstripe_group_result *gr,
+                       cstripe_partial *out)
+{
+    cs_gpu_state *g = s->gpu;
+    const cstripe_reader *r = s->r;
+    GroupParams gp{};
+    gp.base = p;
+    gp.n_group_cols = n_group_cols;
+    for (uint32_t i = 0; i < n_group_cols; i++) {
+        int pj = proj_of(s, (int32_t)group_cols[i]);
+        if (pj < 0) { cs_set_err("group col %u not projected", group_cols[i]); return CSTRIPE_ERR_ARG; }
+        if (r->cols[group_cols[i]].type != CSTRIPE_I8 &&
+            r->cols[group_cols[i]].type != CSTRIPE_TEXT) { cs_set_err("group col %u must be I8 or TEXT", group_cols[i]); return CSTRIPE_ERR_ARG; }
+        gp.gproj[i] = (uint32_t)pj;
+    }
+    gp.n_work = g->n_groups * p.tiles_per_group;
+    if (gp.n_work == 0) {
+        gr->n_groups = 0;
+        s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
+        return CSTRIPE_OK;
+    }
+    const uint32_t n_waves = AGG_BLOCK / WAVE;
+    const uint32_t grid = gp.n_work < GRP_GRID ? gp.n_work : GRP_GRID;
+    if (!g->d_gkeys) {
+        HIP_TRY(hipMalloc(&g->d_gkeys, (uint64_t)GRP_GRID * n_waves * GRP_SLOTS * 4));
+        HIP_TRY(hipMalloc(&g->d_gcells, (uint64_t)GRP_GRID * n_waves * GRP_SLOTS * MAX_AGGS * sizeof(AccCell)));
+        HIP_TRY(hipMalloc(&g->d_gfkeys, CSTRIPE_MAX_GROUPS * 4));
+        HIP_TRY(hipMalloc(&g->d_gfcells, (uint64_t)CSTRIPE_MAX_GROUPS * MAX_AGGS * sizeof(AccCell)));
+        HIP_TRY(hipMalloc(&g->d_gn, 4));
+    }
+    int h_err = 0;
+
+    if (g->all_dense) {
+        /* multi-row grouped kernel (windowed loads + per-wave 16-slot LDS
+         * tables); more than 16 distinct keys in a wave raise flag 8 */
+        const uint32_t mlds = (n_waves * MGRP_SLOTS * n_aggs *
+                               (uint32_t)sizeof(ThreadAcc) + 15u) & ~15u;
+        bool need_decode = g->n_zsegs > 0;
+        for (uint32_t pj = 0; pj < g->n_proj; pj++)
+            if (g->col_scratch[pj]) need_decode = true;
+        HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+        HIP_TRY(hipEventRecord(g->ev0, g->stream));
+        if (need_decode) { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+        HIP_TRY(hipEventRecord(g->ev1, g->stream));
+        auto launchmg = [&](auto *kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(AGG_BLOCK), mlds, g->stream,
+                               g->d_data, g->d_scratch, g->d_groups, g->d_colloc,
+                               g->d_gkeys, g->d_gcells, g->d_error, gp);
+        };
+        if (n_aggs == 5) launchmg(multi_grouped_kernel<5, 8>);
+        else if (n_aggs == 1) launchmg(multi_grouped_kernel<1, 8>);
+        else if (n_aggs == 2) launchmg(multi_grouped_kernel<2, 8>);
+        else if (n_aggs == 4) launchmg(multi_grouped_kernel<4, 8>);
+        else launchmg(multi_grouped_kernel<-1, 4>);
+        HIP_TRY(hipGetLastError());
+        { int _rc = grouped_merge(g, gp, grid, n_waves * MGRP_SLOTS, &h_err); if (_rc != CSTRIPE_OK) return _rc; }
+        if (h_err & 4) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+        if (h_err == 0) return collect_grouped(s, aggs, n_aggs, gr, out);
+        /* flag 8: fall through to the 64-group path */
+    }
+
+    /* any layout, up to CSTRIPE_MAX_GROUPS keys per wave */
+    const uint32_t lds = n_waves * GRP_SLOTS * 4 + n_waves * GRP_SLOTS * n_aggs * (uint32_t)sizeof(ThreadAcc);
+    HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+    HIP_TRY(hipEventRecord(g->ev0, g->stream));
+    { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+    HIP_TRY(hipEventRecord(g->ev1, g->stream));
+    auto launchg = [&](auto *kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(AGG_BLOCK), lds, g->stream,
+                           g->d_data, g->d_scratch, g->d_rank, g->d_groups,
+                           g->d_colloc, g->d_gkeys, g->d_gcells, g->d_error, gp);
+    };
+    if (n_aggs == 5) launchg(grouped_agg_kernel<5>);
+    else if (n_aggs == 1) launchg(grouped_agg_kernel<1>);
+    else if (n_aggs == 2) launchg(grouped_agg_kernel<2>);
+    else launchg(grouped_agg_kernel<-1>);
+    HIP_TRY(hipGetLastError());
+    { int _rc = grouped_merge(g, gp, grid, n_waves * GRP_SLOTS, &h_err); if (_rc != CSTRIPE_OK) return _rc; }
+    if (h_err & 4) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    if (h_err) { cs_set_err("too many distinct groups (device flag %d; caps: %d/wave, %d total)", h_err, GRP_SLOTS, CSTRIPE_MAX_GROUPS); return CSTRIPE_ERR; }
+    return collect_grouped(s, aggs, n_aggs, gr, out);
+}
+
+int csgpu_agg(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+              const uint32_t *group_cols, uint32_t n_group_cols,
+              cstripe_group_result *gr, cstripe_partial *out)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    if (n_aggs > MAX_AGGS) { cs_set_err("too many aggs"); return CSTRIPE_ERR_ARG; }
+    if (s->preds.size() > MAX_PREDS) { cs_set_err("too many preds"); return CSTRIPE_ERR_ARG; }
+
+    AggParams p{};
+    { int _rc = fill_agg_params(s, aggs, n_aggs, p); if (_rc != CSTRIPE_OK) return _rc; }
+    if (n_group_cols > 0)
+        return agg_grouped(s, aggs, n_aggs, group_cols, n_group_cols, p, gr, out);
+    return agg_ungrouped(s, aggs, n_aggs, p, out);
 }
 
 /* =====================================================================
@@ -5898,28 +5161,9 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
 
     HashParams hp{};
     AggParams &p = hp.base;
-    p.n_preds = (uint32_t)s->preds.size();
-    p.n_aggs = n_aggs;
-    p.n_proj = g->n_proj;
-    p.tiles_per_group = (r->head.chunk_row_limit + TILE_ROWS - 1) / TILE_ROWS;
-    if (p.tiles_per_group == 0) p.tiles_per_group = 1;
-    p.n_groups = g->n_groups;
-    fill_preds(s, p);
-    auto proj_of = [&](int32_t col) -> int {
-        if (col < 0 || col >= (int32_t)r->head.column_count) return -1;
-        return g->proj_of_col[col];
-    };
-    for (uint32_t i = 0; i < n_aggs; i++) {
+    for (uint32_t i = 0; i < n_aggs; i++)
         if (aggs[i].kind > CSTRIPE_AGG_SUM_DISC_TAX_I64) { cs_set_err("agg %u: bad kind %u", i, aggs[i].kind); return CSTRIPE_ERR_ARG; }
-        p.aggs[i].kind = (uint8_t)aggs[i].kind;
-        p.aggs[i].one = aggs[i].one;
-        int pa = proj_of(aggs[i].col_a), pb = proj_of(aggs[i].col_b), pc = proj_of(aggs[i].col_c);
-        if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && pa < 0) { cs_set_err("agg %u: col_a not projected", i); return CSTRIPE_ERR_ARG; }
-        if (agg_reads_vartext(r, aggs[i])) { cs_set_err("agg %u: a VARTEXT column can only be the operand of COUNT_COL", i); return CSTRIPE_ERR_ARG; }
-        p.aggs[i].proj_a = (uint8_t)(pa < 0 ? 0 : pa);
-        p.aggs[i].proj_b = (uint8_t)(pb < 0 ? 0 : pb);
-        p.aggs[i].proj_c = (uint8_t)(pc < 0 ? 0 : pc);
-    }
+    { int _rc = fill_agg_params(s, aggs, n_aggs, p); if (_rc != CSTRIPE_OK) return _rc; }
 
     /* key packing: [lo, hi] per key column from the SELECTED chunk groups'
      * skip nodes; total bits <= 63 keeps ~0ull free as the EMPTY marker */
@@ -5947,7 +5191,7 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
     };
     for (uint32_t k = 0; k < n_key_cols; k++) {
         const uint32_t col = key_cols[k];
-        const int pj = proj_of((int32_t)col);
+        const int pj = proj_of(s, (int32_t)col);
         if (col >= r->head.column_count || pj < 0) { cs_set_err("scan_agg_hashed: key col %u not projected", col); return CSTRIPE_ERR_ARG; }
         if (!out->keys[k] || !out->key_nulls[k]) { cs_set_err("scan_agg_hashed: no destination for key col %u", k); return CSTRIPE_ERR_ARG; }
         const uint8_t t = r->cols[col].type;
@@ -6158,29 +5402,9 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
             out->key_nulls[k][oi] = knull[k][i];
             out->keys[k][oi] = kval[k][i];
         }
-        for (uint32_t a = 0; a < n_aggs; a++) {
-            const AccCell &c = h_cells[(size_t)i * n_aggs + a];
-            cstripe_partial o{};
-            o.count = c.cnt;
-            o.is_null = (c.cnt == 0) ? 1 : 0;
-            switch (aggs[a].kind) {
-                case CSTRIPE_AGG_COUNT_STAR:
-                case CSTRIPE_AGG_COUNT_COL:
-                    o.i128_lo = c.cnt; o.is_null = 0; break;
-                case CSTRIPE_AGG_SUM_F64:
-                case CSTRIPE_AGG_MIN_F64:
-                case CSTRIPE_AGG_MAX_F64:
-                    if (!o.is_null) o.f64 = c.f; break;
-                case CSTRIPE_AGG_MIN_I64:
-                case CSTRIPE_AGG_MAX_I64:
-                    if (!o.is_null) { o.i128_lo = c.lo; o.i128_hi = c.lo < 0 ? -1 : 0; }
-                    break;
-                default:
-                    if (!o.is_null) { o.i128_lo = c.lo; o.i128_hi = c.hi; }
-                    break;
-            }
-            out->partials[(size_t)oi * n_aggs + a] = o;
-        }
+        for (uint32_t a = 0; a < n_aggs; a++)
+            out->partials[(size_t)oi * n_aggs + a] =
+                cell_to_partial(aggs[a].kind, h_cells[(size_t)i * n_aggs + a]);
     }
     out->n_groups = n;
     return CSTRIPE_OK;

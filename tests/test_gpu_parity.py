@@ -512,8 +512,10 @@ def test_shard_directory_scan(tmp_path):
 
 def test_fuzz_grouped_differential():
     """Randomized grouped differential fuzz: random i8 key columns, group
-    counts spanning the fused 16-slot cap (exercises fused-grouped AND the
-    >16-group fallback), nullable measures."""
+    counts on both sides of the 16-slot wave tables of multi_grouped_kernel,
+    nullable measures. A draw that leaves a NULL goes straight to
+    grouped_agg_kernel; only a NULL-free draw starts at multi_grouped_kernel
+    (test_gpu_grouped_chain.py reaches that chain deterministically)."""
     import tempfile
     for seed in range(12):
         rng = np.random.default_rng(5000 + seed)
