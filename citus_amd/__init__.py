@@ -245,6 +245,7 @@ _combine_groups = _sig("cagg_combine_groups", C.c_int,
                         C.c_uint64])
 _rewind = _sig("cstripe_scan_rewind", C.c_int, [C.c_void_p])
 _last_fused = _sig("cstripe_scan_last_fused", C.c_int, [C.c_void_p])
+_last_agg_path = _sig("cstripe_scan_last_agg_path", C.c_int, [C.c_void_p])
 _last_kernel_ms = _sig("cstripe_scan_last_kernel_ms", C.c_double, [C.c_void_p])
 _last_decode_ms = _sig("cstripe_scan_last_decode_kernel_ms", C.c_double, [C.c_void_p])
 _last_agg_ms = _sig("cstripe_scan_last_agg_kernel_ms", C.c_double, [C.c_void_p])
@@ -804,6 +805,12 @@ class Scan:
     @property
     def last_fused(self):
         return bool(_last_fused(self._h))
+
+    @property
+    def last_agg_path(self):
+        """body of the last agg(): 0 none/empty, 1 fused, 2 general,
+        3 dense windowed, 4 dense overlapped"""
+        return _last_agg_path(self._h)
 
     @property
     def last_kernel_ms(self):

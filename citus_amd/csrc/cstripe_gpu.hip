@@ -29,6 +29,7 @@
 #include "vartext.h"
 
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstring>
 #include <cstdio>
 #include <vector>
@@ -132,6 +133,11 @@ struct cs_gpu_state {
     uint32_t max_zseg_dlen = 0;      /* largest zstd frame decompressed */
     zr_dtables *d_zrtab = nullptr;   /* predefined FSE decode tables */
     std::vector<uint8_t> col_scratch;/* per proj: any chunk lands in scratch */
+    std::vector<uint8_t> col_ov;     /* per proj: every selected chunk group
+                                      * holds it dense I64 canonical P(L) or
+                                      * CONST (multi_agg_kernel_ov's shapes) */
+    int n_cus = 0;                   /* compute units, sizes the fixed grids */
+    uint32_t max_group_rows = 0;     /* largest selected chunk group */
     int *d_error = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     /* scan_select (filtered row materialisation): per-tile pass masks,
@@ -1355,6 +1361,455 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel(
             AccCell c;
             c.lo = r.lo; c.hi = r.hi; c.f = r.f; c.cnt = r.cnt;
             block_out[(uint64_t)blockIdx.x * n_aggs + a] = c;
+        }
+    }
+}
+
+/* =====================================================================
+ * Dense overlapped body (multi_agg_kernel_ov) — for scans whose every
+ * referenced column is, in every selected chunk group, a dense I64 canonical
+ * P(L) / CONST stream (lz4 or zstd). The host resolves the query into SLOTS
+ * (distinct projected columns, predicate slots first), so a column is loaded
+ * once per row group however many predicates and operands name it.
+ *
+ * A work item is one (chunk group, 2048-row tile): one R=8 row group per
+ * lane. A fixed grid walks items blockIdx.x, +gridDim.x, ... with a plain
+ * for; every trip count follows from n_items. Per item:
+ *   1. the predicate-slot windows (issued one item earlier) are extracted,
+ *   2. the NEXT item's predicate-slot windows are issued back to back,
+ *   3. descriptors are fetched ahead (ColLoc two items, GroupDesc three),
+ *   4. all predicates are evaluated from registers; if any lane of the wave
+ *      passes, the operand-only slots are loaded and the rows folded.
+ * The wait in (4) therefore covers this item's operands and the next item's
+ * predicate windows together: one exposed round trip per item.
+ *
+ * A P(L) value is hval | low-L-bytes with L <= 4, so a row group is held as
+ * 8 u32 per slot; windows are (7*step+4) bytes rounded up to u64 words —
+ * never further than the (7*step+8) windows of col_multi for the same rows.
+ * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
+ * (canon_pos); the one lane holding row 0 fetches them beside its window.
+ * ===================================================================== */
+
+#define OV_R        8                    /* rows per lane per work item */
+#define OV_R_ANY    4                    /* ... of the unspecialised instance:
+                                          * half the registers per row group */
+#define OV_MAX_SLOTS 4
+#define OV_MAX_AGGS 4
+/* u64 words of the widest (step 7) window of an R-row group */
+#define OV_NW(R)    ((((R) - 1) * 7 + 4 + 7) / 8)
+
+struct OvPlan {
+    uint32_t n_items;                    /* n_groups * tiles_pg */
+    uint32_t tiles_pg;                   /* ceil(largest group / (R * AGG_BLOCK)) */
+    uint32_t n_slots, n_pslots;          /* slots [0, n_pslots) carry predicates */
+    uint8_t slot_proj[OV_MAX_SLOTS];
+    /* predicates as whole aligned words, so that a run-time predicate index
+     * is a plain scalar word load: slot | op << 8 | gend << 16, and ival */
+    uint32_t pred_ctl[MAX_PREDS];
+    int64_t pred_val[MAX_PREDS];
+    uint8_t agg_slot[OV_MAX_AGGS][4];    /* slots of proj_a, proj_b, proj_c */
+    uint32_t ksig;                       /* the shape words (ov_sig_*), host */
+    uint64_t sig;                        /* side: pick a specialised instance */
+};
+
+/* one slot of one chunk group, wave-uniform, four SGPRs:
+ * meta = stream offset in d_data (48 bits) | step << 48 | zstd << 56, where
+ * step = bytes between consecutive rows' low bytes (0 = CONST) */
+struct OvCol {
+    uint64_t meta;
+    uint64_t hval;
+};
+
+/* the ColLoc fields ov_col needs, as fetched: the fetch and the packing are
+ * kept a loop trip apart so that no wait sits right behind the scalar loads */
+struct OvRaw {
+    uint64_t val_off;
+    uint64_t hval;
+    uint32_t ml;        /* mode | L << 8 */
+};
+
+__device__ inline OvRaw ov_fetch(const ColLoc &cl)
+{
+    /* mode and L as one aligned word: byte-sized fields would each be a
+     * vector load with a full wait behind it, under the windows in flight */
+    static_assert(offsetof(ColLoc, mode) % 4 == 0 &&
+                  offsetof(ColLoc, L) == offsetof(ColLoc, mode) + 1, "ColLoc layout");
+    OvRaw r;
+    r.val_off = cl.val_off;
+    r.hval = (uint64_t)cl.hval;
+    __builtin_memcpy(&r.ml, &cl.mode, 4);
+    return r;
+}
+
+__device__ inline OvCol ov_col(const OvRaw &r)
+{
+    const uint32_t mode = r.ml & 0xFFu, L = (r.ml >> 8) & 0xFFu;
+    const uint32_t zr = mode >= CSF_SEGMODE_ZRP_BASE ? 1u : 0u;
+    const bool cst = mode == CSF_SEGMODE_CONST || mode == CSF_SEGMODE_ZR_CONST;
+    const uint32_t step = cst ? 0u : (zr ? L : L + 3u);
+    OvCol c;
+    c.meta = r.val_off | ((uint64_t)step << 48) | ((uint64_t)zr << 56);
+    c.hval = r.hval;
+    return c;
+}
+
+__device__ inline uint32_t ov_step(const OvCol &c) { return (uint32_t)(c.meta >> 48) & 0xFFu; }
+__device__ inline uint32_t ov_zr(const OvCol &c) { return (uint32_t)(c.meta >> 56); }
+__device__ inline uint64_t ov_off(const OvCol &c) { return c.meta & 0xFFFFFFFFFFFFull; }
+/* low bytes of row j >= 2 (zstd: j >= 1) start at j*step + ov_off0 (canon_pos) */
+__device__ inline uint32_t ov_off0(uint32_t step, uint32_t zr) { return (zr ? 23u : 9u) - step; }
+/* low-L-bytes mask; 0 for a CONST slot (the value is hval alone) */
+__device__ inline uint32_t ov_mask(uint32_t step, uint32_t zr)
+{
+    const uint32_t L = zr ? step : step - 3u;
+    return step == 0 ? 0u : 0xFFFFFFFFu >> ((4u - L) * 8u);
+}
+
+template <int R, uint32_t STEP>
+__device__ inline void ov_extract(const uint64_t (&w)[OV_NW(R)], uint32_t m,
+                                  uint32_t (&lo)[R])
+{
+    #pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)R; k++) {
+        const uint32_t d = k * STEP, wi = d >> 3, sh = (d & 7u) * 8u;
+        uint32_t x = (uint32_t)(w[wi] >> sh);
+        if (sh > 32u) x |= (uint32_t)(w[wi + 1 < OV_NW(R) ? wi + 1 : wi] << (64u - sh));
+        lo[k] = x & m;
+    }
+}
+
+/* issue one slot's window for the lane's row group (row % R == 0, row inside
+ * the chunk group). Every word is loaded straight into its final register
+ * under a wave-uniform guard, never merged across branches: a merge would
+ * cost a copy, and a copy of a loaded register a wait right behind the load.
+ * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
+ * (canon_pos). The one lane that holds row 0 points word 0 — which only
+ * rows 0/1 of an lz4 window touch, step being >= 4 there — at lz4 row 0, and
+ * loads lz4 row 1 / zstd row 0 into fx.
+ * Word 0 is issued LAST and ov_take reads it on every path, so that one
+ * read stands for "the whole window has landed" (loads return in order):
+ * nothing of a window then counts as outstanding when the next one is
+ * issued into the same registers, and no wait lands between the loads.
+ * ALL (the operand-only slots, whose window is consumed at once): no guards
+ * either — a surplus word re-reads the window's last word, so the reach is
+ * the same and the extraction cannot be sunk in between the loads. */
+template <int R, bool ALL>
+__device__ inline void ov_issue(const uint8_t *__restrict__ data, const OvCol &c,
+                                uint32_t row, uint64_t (&w)[OV_NW(R)], uint32_t &fx)
+{
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    if (step == 0) return;
+    const uint8_t *base = data + ov_off(c);
+    const uint8_t *p = base + (row * step + ov_off0(step, zr));
+    const uint32_t nbytes = (R - 1) * step + 4u;
+    if (row == 0) __builtin_memcpy(&fx, base + (zr ? 15u : 9u), 4);
+    const uint32_t lastw = (nbytes - 1u) >> 3;
+    #pragma unroll
+    for (uint32_t i = OV_NW(R) - 1; i >= 1; i--) {
+        if (ALL) __builtin_memcpy(&w[i], p + 8u * min(i, lastw), 8);
+        else if (8u * i < nbytes) __builtin_memcpy(&w[i], p + 8u * i, 8);
+    }
+    __builtin_memcpy(&w[0], (row == 0 && !zr) ? base + 1 : p, 8);
+    /* keep the scheduler from pulling a first use up between the loads */
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+/* window -> the row group's R low words (value = hval | low word) */
+template <int R>
+__device__ inline void ov_take(const OvCol &c, uint32_t row,
+                               const uint64_t (&w)[OV_NW(R)], uint32_t fx,
+                               uint32_t (&lo)[R])
+{
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    const uint32_t m = ov_mask(step, zr);     /* CONST: any arm, all zero */
+    switch (step) {                           /* wave-uniform */
+        case 1: ov_extract<R, 1>(w, m, lo); break;
+        case 2: ov_extract<R, 2>(w, m, lo); break;
+        case 3: ov_extract<R, 3>(w, m, lo); break;
+        case 4: ov_extract<R, 4>(w, m, lo); break;
+        case 5: ov_extract<R, 5>(w, m, lo); break;
+        case 6: ov_extract<R, 6>(w, m, lo); break;
+        default: ov_extract<R, 7>(w, m, lo); break;
+    }
+    if (row == 0) {
+        if (zr) lo[0] = fx & m;
+        else    lo[1] = fx & m;
+    }
+}
+
+/* slot -> registers: wave-uniform compare chain over compile-time slots */
+template <int R, int NS>
+__device__ inline void ov_pick(const uint32_t (&lo)[NS][R], const OvCol (&c)[NS],
+                               uint32_t slot, uint32_t (&o)[R], uint64_t &h)
+{
+    #pragma unroll
+    for (int s = 0; s < NS; s++)
+        if (slot == (uint32_t)s) {
+            #pragma unroll
+            for (int k = 0; k < R; k++) o[k] = lo[s][k];
+            h = c[s].hval;
+        }
+}
+
+__device__ inline int64_t ov_val(uint32_t lo, uint64_t h) { return (int64_t)((uint64_t)lo | h); }
+
+__device__ inline bool ov_pred(uint8_t op, int64_t iv, int64_t ival)
+{
+    switch (op) {
+        case CSTRIPE_PRED_LT: return iv <  ival;
+        case CSTRIPE_PRED_LE: return iv <= ival;
+        case CSTRIPE_PRED_GT: return iv >  ival;
+        case CSTRIPE_PRED_GE: return iv >= ival;
+        case CSTRIPE_PRED_EQ: return iv == ival;
+        default:              return iv != ival;
+    }
+}
+
+/* integer kinds only: ThreadAcc.f stays the constant acc_init gives them */
+__device__ inline void ov_acc_init(ThreadAcc &a, uint8_t kind)
+{
+    a.lo = kind == CSTRIPE_AGG_MIN_I64 ? INT64_MAX
+         : kind == CSTRIPE_AGG_MAX_I64 ? INT64_MIN : 0;
+    a.hi = 0; a.f = 0.0; a.cnt = 0;
+}
+
+/* a query's shape as compile-time words, for the specialised instances:
+ * SIG  = slot of predicate p at bits [2p, 2p+2), slot of aggregate a's
+ *        operand k at bits [32+6a+2k, +2);  KSIG = kind of aggregate a at
+ *        bits [4a, 4a+4) */
+__host__ __device__ constexpr uint64_t ov_sig_pred(uint32_t p, uint32_t slot)
+{
+    return (uint64_t)slot << (2u * p);
+}
+__host__ __device__ constexpr uint64_t ov_sig_op(uint32_t a, uint32_t k, uint32_t slot)
+{
+    return (uint64_t)slot << (32u + 6u * a + 2u * k);
+}
+__host__ __device__ constexpr uint32_t ov_ksig(uint32_t a, uint32_t kind)
+{
+    return kind << (4u * a);
+}
+
+/* EXACT: the template counts, SIG and KSIG are the query's, so every slot
+ * and kind below is a compile-time constant; otherwise the counts are
+ * capacities and everything comes from the plan / params through
+ * wave-uniform guards */
+template <int R, int NS, int NPS, int NPREDS, int NAGGS, bool EXACT, int MINW,
+          uint64_t SIG = 0, uint32_t KSIG = 0>
+__global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
+    const uint8_t *__restrict__ data, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, AccCell *__restrict__ block_out,
+    const AggParams params, const OvPlan plan)
+{
+    constexpr uint32_t TILE = R * AGG_BLOCK;
+    const uint32_t ns = EXACT ? (uint32_t)NS : plan.n_slots;
+    const uint32_t nps = EXACT ? (uint32_t)NPS : plan.n_pslots;
+    const uint32_t n_preds = EXACT ? (uint32_t)NPREDS : params.n_preds;
+    const uint32_t n_aggs = EXACT ? (uint32_t)NAGGS : params.n_aggs;
+    const uint32_t n_items = plan.n_items, tpg = plan.tiles_pg;
+    const uint32_t G = gridDim.x, last = n_items - 1u;
+    const uint32_t lrow = R * threadIdx.x;
+
+    ThreadAcc acc[NAGGS];
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) ov_acc_init(acc[a], params.aggs[a].kind);
+
+    /* prologue: the block's first item, and the descriptors behind it */
+    uint32_t it = blockIdx.x;
+    OvCol c[NS] = {};
+    uint32_t crc = 0, crow = 0;
+    uint64_t wn[NS][OV_NW(R)] = {};
+    uint32_t fx[NS] = {};
+    if (it < n_items) {
+        const GroupDesc g0 = groups[it / tpg];
+        crc = g0.row_count;
+        crow = (it % tpg) * TILE + lrow;
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < ns) c[s] = ov_col(ov_fetch(colloc[g0.colbase + plan.slot_proj[s]]));
+        if (crow < crc) {
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s < nps) ov_issue<R, false>(data, c[s], crow, wn[s], fx[s]);
+        }
+    }
+    /* indices past the end are clamped for the descriptor reads only; no
+     * window is ever issued for an item that does not exist */
+    const GroupDesc g1 = groups[min(it + G, last) / tpg];
+    OvCol nc[NS] = {};
+    #pragma unroll
+    for (int s = 0; s < NS; s++)
+        if ((uint32_t)s < ns) nc[s] = ov_col(ov_fetch(colloc[g1.colbase + plan.slot_proj[s]]));
+    uint32_t nrc = g1.row_count;
+    GroupDesc g2 = groups[min(it + 2u * G, last) / tpg];
+
+    for (; it < n_items; it += G) {
+        /* 1. this item's predicate slots: windows -> R x u32 per slot */
+        uint32_t lo[NS][R];
+        const bool active = crow < crc;
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < nps) ov_take<R>(c[s], crow, wn[s], fx[s], lo[s]);
+
+        /* 2. next item's predicate windows, all slots back to back */
+        const uint32_t it1 = it + G;
+        const uint32_t nrow = (min(it1, last) % tpg) * TILE + lrow;
+        if (it1 < n_items && nrow < nrc) {
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s < nps) ov_issue<R, false>(data, nc[s], nrow, wn[s], fx[s]);
+        }
+
+        /* 3. descriptors: ColLocs of item +2 (its GroupDesc came one trip
+         * ago), GroupDesc of item +3 */
+        OvRaw nn[NS] = {};
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < ns) nn[s] = ov_fetch(colloc[g2.colbase + plan.slot_proj[s]]);
+        const uint32_t nnrc = g2.row_count;
+        const GroupDesc g3 = groups[min(it + 3u * G, last) / tpg];
+
+        /* 4. every predicate from registers; row-pass flags as a bitmask */
+        uint32_t pv = 0;
+        if (active) {
+            const uint32_t left = crc - crow;
+            pv = left >= (uint32_t)R ? (1u << R) - 1u : (1u << left) - 1u;
+        }
+        uint32_t gv = 0;
+        #pragma unroll
+        for (uint32_t p = 0; p < (EXACT ? (uint32_t)NPREDS : n_preds); p++) {
+            const uint32_t ctl = plan.pred_ctl[p];
+            const int64_t ival = plan.pred_val[p];
+            uint32_t o[R]; uint64_t h = 0;
+            ov_pick<R, NS>(lo, c, EXACT ? (uint32_t)(SIG >> (2u * p)) & 3u
+                                        : ctl & 0xFFu, o, h);
+            #pragma unroll
+            for (int k = 0; k < R; k++)
+                gv |= (uint32_t)ov_pred((uint8_t)(ctl >> 8), ov_val(o[k], h), ival) << k;
+            if (ctl >> 16) { pv &= gv; gv = 0; }
+        }
+
+        if (__ballot(pv != 0) != 0) {
+            /* operand-only slots: loaded only when some row of the wave passed */
+            if (active) {
+                #pragma unroll
+                for (int s = 0; s < NS; s++)
+                    if ((uint32_t)s >= nps && (uint32_t)s < ns) {
+                        uint64_t w[OV_NW(R)] = {};
+                        uint32_t f = 0;
+                        ov_issue<R, true>(data, c[s], crow, w, f);
+                        ov_take<R>(c[s], crow, w, f, lo[s]);
+                    }
+            }
+            const int64_t cnt = __popc(pv);
+            #pragma unroll
+            for (int a = 0; a < NAGGS; a++) {
+                if (!EXACT && (uint32_t)a >= n_aggs) continue;
+                const AggD &g = params.aggs[a];
+                uint32_t oa[R], ob[R], oc[R];
+                uint64_t ha = 0, hb = 0, hc = 0;
+                const uint32_t sa = EXACT ? (uint32_t)(SIG >> (32u + 6u * a)) & 3u
+                                          : (uint32_t)plan.agg_slot[a][0];
+                const uint32_t sb = EXACT ? (uint32_t)(SIG >> (34u + 6u * a)) & 3u
+                                          : (uint32_t)plan.agg_slot[a][1];
+                const uint32_t sc = EXACT ? (uint32_t)(SIG >> (36u + 6u * a)) & 3u
+                                          : (uint32_t)plan.agg_slot[a][2];
+                const uint32_t kind = EXACT ? (KSIG >> (4u * a)) & 15u : (uint32_t)g.kind;
+                switch (kind) {                   /* values already in registers */
+                    case CSTRIPE_AGG_COUNT_STAR:
+                        acc[a].lo += cnt;
+                        break;
+                    case CSTRIPE_AGG_SUM_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u) t += (__int128)ov_val(oa[k], ha);
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    case CSTRIPE_AGG_MIN_I64:
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u) acc[a].lo = min(acc[a].lo, ov_val(oa[k], ha));
+                        break;
+                    case CSTRIPE_AGG_MAX_I64:
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u) acc[a].lo = max(acc[a].lo, ov_val(oa[k], ha));
+                        break;
+                    case CSTRIPE_AGG_SUM_PROD_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u)
+                                t += (__int128)ov_val(oa[k], ha) * ov_val(ob[k], hb);
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    case CSTRIPE_AGG_SUM_DISC_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u)
+                                t += (__int128)ov_val(oa[k], ha) * (g.one - ov_val(ob[k], hb));
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    case CSTRIPE_AGG_SUM_DISC_TAX_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        ov_pick<R, NS>(lo, c, sc, oc, hc);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u)
+                                t += (__int128)ov_val(oa[k], ha) * (g.one - ov_val(ob[k], hb))
+                                     * (g.one + ov_val(oc[k], hc));
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    default:
+                        break;
+                }
+                acc[a].cnt += cnt;
+            }
+        }
+
+        /* rotate the descriptor pipeline; the ColLocs fetched in (3) are
+         * first touched here, a whole fold later */
+        #pragma unroll
+        for (int s = 0; s < NS; s++) { c[s] = nc[s]; nc[s] = ov_col(nn[s]); }
+        crc = nrc; crow = nrow;
+        nrc = nnrc;
+        g2 = g3;
+    }
+
+    /* one wave/block reduce per block */
+    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][NAGGS];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+        if (!EXACT && (uint32_t)a >= n_aggs) continue;
+        wave_reduce(acc[a], params.aggs[a].kind);
+        if (lane == 0) lds[wid][a] = acc[a];
+    }
+    __syncthreads();
+    if (wid == 0) {
+        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
+            ThreadAcc r = lds[0][a];
+            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
+                acc_merge(r, lds[w][a], params.aggs[a].kind);
+            AccCell cell;
+            cell.lo = r.lo; cell.hi = r.hi; cell.f = r.f; cell.cnt = r.cnt;
+            block_out[(uint64_t)blockIdx.x * n_aggs + a] = cell;
         }
     }
 }
@@ -2847,7 +3302,11 @@ int csgpu_stage(cstripe_scan *s, int device_id)
     HIP_TRY(hipEventCreate(&g->ev2));
     data_bytes += 128;              /* window read slack: R-row extraction
                                      * windows reach up to ~60 B past the
-                                     * last region's stream end */
+                                     * last region's stream end. Sized for
+                                     * the R=8 windows of col_multi and
+                                     * multi_agg_kernel_ov (ov_load): a larger
+                                     * R or a wider window there needs a
+                                     * larger slack here */
     if (data_bytes) HIP_TRY(hipMalloc(&g->d_data, data_bytes));
     if (scratch_bytes) HIP_TRY(hipMalloc(&g->d_scratch, scratch_bytes));
     if (rank_words) HIP_TRY(hipMalloc(&g->d_rank, rank_words * 4));
@@ -3139,6 +3598,26 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                                hipMemcpyHostToDevice, g->stream));
     }
     HIP_TRY(hipStreamSynchronize(g->stream));
+    /* which projected columns the overlapped dense body can read: one pass
+     * over the descriptors just built */
+    g->col_ov.assign(n_proj, 1);
+    for (uint64_t i = 0; i < h_colloc.size(); i++) {
+        const ColLoc &cl = h_colloc[i];
+        const bool shape =
+            cl.mode == CSF_SEGMODE_CONST || cl.mode == CSF_SEGMODE_ZR_CONST ||
+            (((cl.mode & 0xF0u) == CSF_SEGMODE_P_BASE ||
+              (cl.mode & 0xF0u) == CSF_SEGMODE_ZRP_BASE) &&
+             (cl.mode & 0xFu) >= 1 && (cl.mode & 0xFu) <= 4 && cl.L == (cl.mode & 0xFu));
+        if (!((cl.flags & 2) && (cl.flags & 4) && !(cl.flags & 1) &&
+              cl.type == CSTRIPE_I64 && shape))
+            g->col_ov[i % n_proj] = 0;
+    }
+    g->max_group_rows = 0;
+    for (const GroupDesc &gd : h_groups)
+        if (gd.row_count > g->max_group_rows) g->max_group_rows = gd.row_count;
+    if (hipDeviceGetAttribute(&g->n_cus, hipDeviceAttributeMultiprocessorCount,
+                              g->device) != hipSuccess || g->n_cus <= 0)
+        g->n_cus = 256;
     g->colloc_host = h_colloc;
     s->text_dicts.clear();
     s->last_text_decode_ms = s->last_text_walk_ms = 0;
@@ -3938,6 +4417,79 @@ static int collect_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
     return CSTRIPE_OK;
 }
 
+/* waves per SIMD of multi_agg_kernel_ov = resident blocks per CU (a block is
+ * one wave per SIMD); with the CU count this sizes its fixed grid */
+#define OV_WAVES 4
+
+/* resolve one scan_agg into the overlapped dense body's plan: the distinct
+ * projected columns it touches (predicate slots first, each column once) and
+ * the slot of every predicate and aggregate operand. false = not eligible,
+ * the caller keeps the windowed body. */
+static bool ov_build_plan(const cstripe_scan *s, const AggParams &p, OvPlan &pl)
+{
+    const cs_gpu_state *g = s->gpu;
+    memset(&pl, 0, sizeof(pl));
+    if (!g->all_dense || p.n_preds == 0 || p.n_preds > MAX_PREDS ||
+        p.n_aggs == 0 || p.n_aggs > OV_MAX_AGGS || g->col_ov.size() != g->n_proj)
+        return false;
+    int slot_of[MAX_PROJ];
+    for (int i = 0; i < MAX_PROJ; i++) slot_of[i] = -1;
+    auto slot = [&](uint32_t proj) -> int {
+        if (proj >= g->n_proj || !g->col_ov[proj]) return -1;
+        if (slot_of[proj] < 0) {
+            if (pl.n_slots == OV_MAX_SLOTS) return -1;
+            pl.slot_proj[pl.n_slots] = (uint8_t)proj;
+            slot_of[proj] = (int)pl.n_slots++;
+        }
+        return slot_of[proj];
+    };
+    for (uint32_t i = 0; i < p.n_preds; i++) {
+        if (p.preds[i].is_float) return false;
+        const int sl = slot(p.preds[i].proj);
+        if (sl < 0) return false;
+        pl.pred_ctl[i] = (uint32_t)sl | ((uint32_t)p.preds[i].op << 8) |
+                         ((uint32_t)(p.preds[i].gend ? 1 : 0) << 16);
+        pl.pred_val[i] = p.preds[i].ival;
+        pl.sig |= ov_sig_pred(i, (uint32_t)sl);
+    }
+    pl.n_pslots = pl.n_slots;
+    for (uint32_t a = 0; a < p.n_aggs; a++) {
+        const AggD &ag = p.aggs[a];
+        uint32_t n_ops;
+        switch (ag.kind) {
+            case CSTRIPE_AGG_COUNT_STAR:       n_ops = 0; break;
+            case CSTRIPE_AGG_SUM_I64:
+            case CSTRIPE_AGG_MIN_I64:
+            case CSTRIPE_AGG_MAX_I64:          n_ops = 1; break;
+            case CSTRIPE_AGG_SUM_PROD_I64:
+            case CSTRIPE_AGG_SUM_DISC_I64:     n_ops = 2; break;
+            case CSTRIPE_AGG_SUM_DISC_TAX_I64: n_ops = 3; break;
+            default: return false;
+        }
+        const uint8_t ops[3] = {ag.proj_a, ag.proj_b, ag.proj_c};
+        for (uint32_t k = 0; k < n_ops; k++) {
+            const int sl = slot(ops[k]);
+            if (sl < 0) return false;
+            pl.agg_slot[a][k] = (uint8_t)sl;
+            pl.sig |= ov_sig_op(a, k, (uint32_t)sl);
+        }
+        pl.ksig |= ov_ksig(a, ag.kind);
+    }
+    if (g->max_group_rows >= (1u << 28)) return false;   /* row * step stays u32 */
+    /* work items at the finest tiling any instance uses */
+    const uint64_t tiles = (g->max_group_rows + OV_R_ANY * AGG_BLOCK - 1) / (OV_R_ANY * AGG_BLOCK);
+    if (g->n_groups == 0 || g->n_groups * (tiles ? tiles : 1) >= (1ull << 31)) return false;
+    return true;
+}
+
+/* the plan's work items for an instance that takes R rows per lane */
+static void ov_set_tiling(const cs_gpu_state *g, OvPlan &pl, uint32_t R)
+{
+    pl.tiles_pg = (g->max_group_rows + R * AGG_BLOCK - 1) / (R * AGG_BLOCK);
+    if (pl.tiles_pg == 0) pl.tiles_pg = 1;
+    pl.n_items = g->n_groups * pl.tiles_pg;
+}
+
 static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
                          uint32_t n_aggs, const AggParams &p, cstripe_partial *out)
 {
@@ -3948,6 +4500,7 @@ static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
         for (uint32_t a = 0; a < n_aggs; a++)
             out[a] = cell_to_partial(aggs[a].kind, AccCell{});
         s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
+        s->last_agg_path = CSTRIPE_AGG_PATH_NONE;
         return CSTRIPE_OK;
     }
 
@@ -3957,6 +4510,7 @@ static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
         /* fused decode+filter+aggregate: no scratch round trip; the first
          * stage time is the fused kernel (decode dominates) */
         s->last_fused = 1;
+        s->last_agg_path = CSTRIPE_AGG_PATH_FUSED;
         auto launchf = [&](auto *kern) {
             hipLaunchKernelGGL(kern, dim3(g->n_tiles), dim3(AGG_BLOCK),
                                AGG_BLOCK * FUSE_STRIDE, g->stream,
@@ -3976,6 +4530,49 @@ static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
         s->last_fused = 0;
         { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
         HIP_TRY(hipEventRecord(g->ev1, g->stream));
+        OvPlan pl;
+        if (ov_build_plan(s, p, pl)) {
+            /* every referenced column is canonical P(L)/CONST everywhere:
+             * overlapped body on a fixed, device-sized grid; each block
+             * leaves one partial per aggregate */
+            s->last_agg_path = CSTRIPE_AGG_PATH_DENSE_OV;
+            uint32_t grid = 0;
+            auto launcho = [&](auto *kern, uint32_t R) {
+                ov_set_tiling(g, pl, R);
+                grid = (uint32_t)g->n_cus * OV_WAVES;
+                if (grid > pl.n_items) grid = pl.n_items;
+                if (grid > g->max_blocks) grid = g->max_blocks;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(AGG_BLOCK), 0, g->stream,
+                                   g->d_data, g->d_groups, g->d_colloc, g->d_block,
+                                   p, pl);
+            };
+            /* specialised shapes: TPC-H Q6 (two range predicates on one
+             * column, two on a second, one on a third; sum(a*b) with b the
+             * second column, count(*)) and count(*) under one predicate */
+            constexpr uint64_t SIG_Q6 =
+                ov_sig_pred(0, 0) | ov_sig_pred(1, 0) | ov_sig_pred(2, 1) |
+                ov_sig_pred(3, 1) | ov_sig_pred(4, 2) |
+                ov_sig_op(0, 0, 3) | ov_sig_op(0, 1, 1);
+            constexpr uint32_t KSIG_Q6 = ov_ksig(0, CSTRIPE_AGG_SUM_PROD_I64) |
+                                         ov_ksig(1, CSTRIPE_AGG_COUNT_STAR);
+            constexpr uint32_t KSIG_CNT = ov_ksig(0, CSTRIPE_AGG_COUNT_STAR);
+            if (pl.n_slots == 4 && pl.n_pslots == 3 && p.n_preds == 5 && n_aggs == 2 &&
+                pl.sig == SIG_Q6 && pl.ksig == KSIG_Q6)
+                launcho(multi_agg_kernel_ov<OV_R, 4, 3, 5, 2, true, OV_WAVES,
+                                            SIG_Q6, KSIG_Q6>, OV_R);
+            else if (pl.n_slots == 1 && p.n_preds == 1 && n_aggs == 1 &&
+                     pl.sig == 0 && pl.ksig == KSIG_CNT)
+                launcho(multi_agg_kernel_ov<OV_R, 1, 1, 1, 1, true, OV_WAVES,
+                                            0, KSIG_CNT>, OV_R);
+            else
+                launcho(multi_agg_kernel_ov<OV_R_ANY, OV_MAX_SLOTS, OV_MAX_SLOTS, 0,
+                                            OV_MAX_AGGS, false, OV_WAVES>, OV_R_ANY);
+            HIP_TRY(hipGetLastError());
+            { int _rc = launch_final_reduce(g, grid, p); if (_rc != CSTRIPE_OK) return _rc; }
+            HIP_TRY(hipEventRecord(g->ev2, g->stream));
+            return collect_ungrouped(s, aggs, n_aggs, out);
+        }
+        s->last_agg_path = g->all_dense ? CSTRIPE_AGG_PATH_DENSE : CSTRIPE_AGG_PATH_GENERAL;
         if (g->all_dense) {
             /* all-dense: R-row windowed kernel (canonical closed-form or
              * decoded/raw typed arrays); hot shapes run R8 at a forced

@@ -78,6 +78,7 @@ struct cstripe_scan {
     cs_gpu_state *gpu = nullptr;
     size_t batch_pos = 0;             /* next_batch cursor into sel */
     int last_fused = 0;
+    int last_agg_path = 0;            /* CSTRIPE_AGG_PATH_* of the last scan_agg */
     double last_kernel_ms = 0.0;
     double last_decode_ms = 0.0;
     double last_agg_ms = 0.0;

@@ -660,6 +660,14 @@ int cstripe_scan_last_hash_ms(const cstripe_scan *s, double *init_ms, double *sc
  * kernel (no scratch round trip), 0 for the two-kernel path */
 int cstripe_scan_last_fused(const cstripe_scan *s);
 
+/* which kernel body the last cstripe_scan_agg ran */
+#define CSTRIPE_AGG_PATH_NONE       0   /* no call yet, or an empty selection */
+#define CSTRIPE_AGG_PATH_FUSED      1   /* fused decode+filter+aggregate */
+#define CSTRIPE_AGG_PATH_GENERAL    2   /* per-row kernel (NULLs present) */
+#define CSTRIPE_AGG_PATH_DENSE      3   /* dense, R-row windows per column */
+#define CSTRIPE_AGG_PATH_DENSE_OV   4   /* dense, overlapped column loads */
+int cstripe_scan_last_agg_path(const cstripe_scan *s);
+
 /* per-call timing of the last cstripe_scan_agg: kernel time (hipEvents, on the
  * scan's stream) and wall time inside the call, milliseconds. */
 double cstripe_scan_last_kernel_ms(const cstripe_scan *s);
