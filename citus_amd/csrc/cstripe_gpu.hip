@@ -1378,8 +1378,10 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel(
  *   1. the predicate-slot windows (issued one item earlier) are extracted,
  *   2. the NEXT item's predicate-slot windows are issued back to back,
  *   3. descriptors are fetched ahead (ColLoc two items, GroupDesc three),
- *   4. all predicates are evaluated from registers; if any lane of the wave
- *      passes, the operand-only slots are loaded and the rows folded.
+ *   4. all predicates are evaluated from registers, each as one unsigned
+ *      32-bit range test of the row's low word (ov_cmp); if any lane of the
+ *      wave passes, the lanes that hold a passing row load the operand-only
+ *      slots and fold their rows.
  * The wait in (4) therefore covers this item's operands and the next item's
  * predicate windows together: one exposed round trip per item.
  *
@@ -1553,16 +1555,76 @@ __device__ inline void ov_pick(const uint32_t (&lo)[NS][R], const OvCol (&c)[NS]
 
 __device__ inline int64_t ov_val(uint32_t lo, uint64_t h) { return (int64_t)((uint64_t)lo | h); }
 
-__device__ inline bool ov_pred(uint8_t op, int64_t iv, int64_t ival)
+/* the low-word mask of a slot: the largest low word any of its rows holds */
+template <int NS>
+__device__ inline uint32_t ov_pick_mask(const OvCol (&c)[NS], uint32_t slot)
 {
-    switch (op) {
-        case CSTRIPE_PRED_LT: return iv <  ival;
-        case CSTRIPE_PRED_LE: return iv <= ival;
-        case CSTRIPE_PRED_GT: return iv >  ival;
-        case CSTRIPE_PRED_GE: return iv >= ival;
-        case CSTRIPE_PRED_EQ: return iv == ival;
-        default:              return iv != ival;
+    uint32_t m = 0;
+    #pragma unroll
+    for (int s = 0; s < NS; s++)
+        if (slot == (uint32_t)s) m = ov_mask(ov_step(c[s]), ov_zr(c[s]));
+    return m;
+}
+
+/* SUM_PROD of a specialised instance takes a narrow fold when, for the whole
+ * row group, both operands are their low words alone (hval == 0, so neither
+ * is negative) and their widths add to at most 61 bits: a product is then
+ * below 2^61 and eight of them below 2^64, so the row group folds in one u64
+ * with 32-bit multiply-adds (a failing row adds 0) and meets the 128-bit
+ * accumulator once. Wave-uniform; anything else takes the 128-bit fold, and
+ * so does the unspecialised instance, which the second fold made slower
+ * (registers spilled: DESIGN section 3). */
+#define OV_NARROW_BITS 61u
+
+/* row k's low word if the row passed, else 0 */
+__device__ inline uint32_t ov_sel(uint32_t pv, int k, uint32_t x)
+{
+    return ((pv >> k) & 1u) ? x : 0u;
+}
+
+/* one predicate against one slot of one chunk group, reduced on the scalar
+ * side (op, hval and ival are all wave-uniform) to an unsigned range test of
+ * the row's low word: the row passes iff ((lo - a) <= d) != inv.
+ * A value is hval | lo with lo a u32, so its high word is hval's: where that
+ * differs from ival's (as signed words) the predicate is constant for the row
+ * group; where it is equal the low words x = lo | (u32)hval decide, unsigned,
+ * and the predicate holds on a range [A, B] of x or on its complement.
+ * hval has the slot's low L bytes clear (and a CONST slot's lo is 0), so
+ * x = lo + (u32)hval and the bias folds into a. Exact for every int64 ival. */
+struct OvCmp {
+    uint32_t a, d, inv;
+};
+
+__device__ inline OvCmp ov_cmp(uint32_t op, uint64_t hval, int64_t ival)
+{
+    const int32_t vh = (int32_t)(hval >> 32), ih = (int32_t)((uint64_t)ival >> 32);
+    const uint32_t t = (uint32_t)ival;
+    uint32_t A = 0, B = 0xFFFFFFFFu;
+    bool none = false, inv = false;
+    if (vh != ih) {
+        const bool less = vh < ih;            /* every row < ival, or every row > */
+        switch (op) {
+            case CSTRIPE_PRED_LT: case CSTRIPE_PRED_LE: none = !less; break;
+            case CSTRIPE_PRED_GT: case CSTRIPE_PRED_GE: none = less; break;
+            case CSTRIPE_PRED_EQ: none = true; break;
+            default: break;
+        }
+    } else {
+        switch (op) {
+            case CSTRIPE_PRED_LT: none = t == 0; B = t - 1u; break;
+            case CSTRIPE_PRED_LE: B = t; break;
+            case CSTRIPE_PRED_GT: none = t == 0xFFFFFFFFu; A = t + 1u; break;
+            case CSTRIPE_PRED_GE: A = t; break;
+            case CSTRIPE_PRED_EQ: A = B = t; break;
+            default: A = B = t; inv = true; break;
+        }
     }
+    if (none) { A = 0; B = 0xFFFFFFFFu; inv = true; }
+    OvCmp r;
+    r.a = A - (uint32_t)hval;
+    r.d = B - A;
+    r.inv = inv ? 1u : 0u;
+    return r;
 }
 
 /* integer kinds only: ThreadAcc.f stays the constant acc_init gives them */
@@ -1683,24 +1745,29 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
             uint32_t o[R]; uint64_t h = 0;
             ov_pick<R, NS>(lo, c, EXACT ? (uint32_t)(SIG >> (2u * p)) & 3u
                                         : ctl & 0xFFu, o, h);
+            const OvCmp cm = ov_cmp((ctl >> 8) & 0xFFu, h, ival);
+            uint32_t g = 0;
             #pragma unroll
             for (int k = 0; k < R; k++)
-                gv |= (uint32_t)ov_pred((uint8_t)(ctl >> 8), ov_val(o[k], h), ival) << k;
+                g |= (uint32_t)(o[k] - cm.a <= cm.d) << k;
+            gv |= g ^ ((0u - cm.inv) & ((1u << R) - 1u));
             if (ctl >> 16) { pv &= gv; gv = 0; }
         }
 
-        if (__ballot(pv != 0) != 0) {
-            /* operand-only slots: loaded only when some row of the wave passed */
-            if (active) {
-                #pragma unroll
-                for (int s = 0; s < NS; s++)
-                    if ((uint32_t)s >= nps && (uint32_t)s < ns) {
-                        uint64_t w[OV_NW(R)] = {};
-                        uint32_t f = 0;
-                        ov_issue<R, true>(data, c[s], crow, w, f);
-                        ov_take<R>(c[s], crow, w, f, lo[s]);
-                    }
-            }
+        /* the wave-level test is the uniform branch round the whole fold;
+         * inside it only the lanes that hold a passing row go on (pv != 0
+         * implies active): they alone load the operand-only slots, so a
+         * 128-B line no passing lane reaches is never fetched, and a lane
+         * with nothing to add folds nothing */
+        if (__ballot(pv != 0) != 0 && pv != 0) {
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s >= nps && (uint32_t)s < ns) {
+                    uint64_t w[OV_NW(R)] = {};
+                    uint32_t f = 0;
+                    ov_issue<R, true>(data, c[s], crow, w, f);
+                    ov_take<R>(c[s], crow, w, f, lo[s]);
+                }
             const int64_t cnt = __popc(pv);
             #pragma unroll
             for (int a = 0; a < NAGGS; a++) {
@@ -1743,6 +1810,16 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
                     case CSTRIPE_AGG_SUM_PROD_I64: {
                         ov_pick<R, NS>(lo, c, sa, oa, ha);
                         ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        if (EXACT && (ha | hb) == 0 &&
+                            __popc(ov_pick_mask<NS>(c, sa)) + __popc(ov_pick_mask<NS>(c, sb))
+                                <= OV_NARROW_BITS) {
+                            uint64_t u = 0;
+                            #pragma unroll
+                            for (int k = 0; k < R; k++)
+                                u += (uint64_t)ov_sel(pv, k, oa[k]) * ob[k];
+                            acc_add_i128(acc[a], (__int128)u);
+                            break;
+                        }
                         __int128 t = 0;
                         #pragma unroll
                         for (int k = 0; k < R; k++)
