@@ -45,6 +45,10 @@ VARTEXT_MAX_LEN = 65535
 VARTEXT_MAX_DISTINCT = 1 << 20
 COMP_NONE, COMP_PGLZ, COMP_LZ4, COMP_ZSTD = 0, 1, 2, 3
 PRED_LT, PRED_LE, PRED_GT, PRED_GE, PRED_EQ, PRED_NE = range(6)
+PRED_IN, PRED_NOT_IN = 6, 7      # value is a set (see make_preds_sets)
+MAX_SETS = 4
+MAX_SET_VALUES = 1 << 26
+SET_FORM_NONE, SET_FORM_HASH, SET_FORM_BITMAP = 0, 1, 2
 (AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM_I64, AGG_SUM_F64,
  AGG_MIN_I64, AGG_MAX_I64, AGG_MIN_F64, AGG_MAX_F64,
  AGG_SUM_PROD_I64, AGG_SUM_DISC_I64, AGG_SUM_DISC_TAX_I64) = range(11)
@@ -79,6 +83,11 @@ class VarTextIn(C.Structure):
 
 class TextConst(C.Structure):
     _fields_ = [("data", C.c_char_p), ("len", C.c_uint32)]
+
+
+class ValueSet(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("texts", C.POINTER(TextConst)),
+                ("n", C.c_uint64), ("on_device", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class AggSpec(C.Structure):
@@ -197,6 +206,14 @@ _scan_begin = _sig("cstripe_scan_begin", C.c_void_p,
 _scan_begin_ex = _sig("cstripe_scan_begin_ex", C.c_void_p,
                       [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32,
                        C.POINTER(TextConst), C.c_uint32])
+_scan_begin_sets = _sig("cstripe_scan_begin_sets", C.c_void_p,
+                        [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32,
+                         C.POINTER(TextConst), C.c_uint32,
+                         C.POINTER(ValueSet), C.c_uint32])
+_last_set_ms = _sig("cstripe_scan_last_set_ms", C.c_int,
+                    [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)])
+_set_form = _sig("cstripe_scan_set_form", C.c_int,
+                 [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)])
 _vartext_validate = _sig("cstripe_vartext_validate", C.c_int,
                          [C.c_char_p, C.c_uint64, C.c_uint32])
 _text_dict = _sig("cstripe_scan_text_dict", C.c_int,
@@ -568,6 +585,67 @@ def make_preds_ex(preds):
     return arr, tc, len(texts)
 
 
+def _is_set_pred(p):
+    return p[1] in (PRED_IN, PRED_NOT_IN)
+
+
+def make_preds_sets(preds):
+    """make_preds_ex plus the value sets of (col, PRED_IN | PRED_NOT_IN,
+    values[, or_group]) predicates. `values` is a sequence / ndarray of ints
+    (TEXT columns: text_slots() output), a list of bytes / str (a VARTEXT
+    column), or a contiguous int64 torch tensor on the GPU, which becomes a
+    device set read in place. The same `values` object given to several
+    predicates is one set. Returns (Pred array, TextConst array or None,
+    n_text_consts, ValueSet array or None, n_sets); the arrays keep every
+    buffer they point at alive."""
+    import numpy as np
+    plain = [(p[0], p[1], 0) + tuple(p[3:4]) if _is_set_pred(p) else p for p in preds]
+    arr, tc, n_tc = make_preds_ex(plain)
+    sets, keep, index = [], [], {}
+    for i, p in enumerate(preds):
+        if not _is_set_pred(p):
+            continue
+        v = p[2]
+        if id(v) in index:
+            arr[i].ival = index[id(v)]
+            continue
+        vs = ValueSet()
+        if type(v).__module__.split(".")[0] == "torch":
+            if not v.is_cuda or str(v.dtype) != "torch.int64" or not v.is_contiguous():
+                raise CStripeError("PRED_IN: a tensor set must be a contiguous int64 "
+                                   "tensor on the GPU")
+            import torch
+            torch.cuda.synchronize(v.device)
+            vs.values = v.data_ptr() if v.numel() else None
+            vs.n = v.numel()
+            vs.on_device = 1
+            keep.append(v)
+        elif (not isinstance(v, np.ndarray) and len(v) > 0 and
+              all(isinstance(x, (bytes, bytearray, str)) for x in v)):
+            bs = [x.encode() if isinstance(x, str) else bytes(x) for x in v]
+            ta = (TextConst * len(bs))()
+            for k, b in enumerate(bs):
+                ta[k].data = b
+                ta[k].len = len(b)
+            vs.texts = ta
+            vs.n = len(bs)
+            keep.append((ta, bs))
+        else:
+            a = np.ascontiguousarray(np.asarray(v).astype(np.int64, copy=False)
+                                     if len(v) else np.zeros(0, np.int64))
+            vs.values = a.ctypes.data_as(C.c_void_p).value if len(a) else None
+            vs.n = len(a)
+            keep.append(a)
+        index[id(v)] = len(sets)
+        arr[i].ival = len(sets)
+        sets.append(vs)
+    if not sets:
+        return arr, tc, n_tc, None, 0
+    sa = (ValueSet * len(sets))(*sets)
+    sa._keep = keep
+    return arr, tc, n_tc, sa, len(sets)
+
+
 def agg_cols_mask(aggs):
     """Projection bitmask covering every column the agg specs read — the
     caller-side analog of ColumnarAttrNeeded (columnar_customscan.c:1813-1851):
@@ -765,12 +843,18 @@ def merge_topn(results, order, limit, offset=0, text=False):
 
 class Scan:
     def __init__(self, reader, cols_mask, preds):
-        self._preds, self._texts, n_texts = make_preds_ex(preds)
-        if n_texts:     # string constants: VARTEXT predicates
-            self._h = _scan_begin_ex(reader._h, cols_mask, self._preds, len(preds),
-                                     self._texts, n_texts)
+        self._sets = None
+        if any(_is_set_pred(p) for p in preds):   # IN / NOT IN: value sets
+            self._preds, self._texts, n_texts, self._sets, n_sets = make_preds_sets(preds)
+            self._h = _scan_begin_sets(reader._h, cols_mask, self._preds, len(preds),
+                                       self._texts, n_texts, self._sets, n_sets)
         else:
-            self._h = _scan_begin(reader._h, cols_mask, self._preds, len(preds))
+            self._preds, self._texts, n_texts = make_preds_ex(preds)
+            if n_texts:     # string constants: VARTEXT predicates
+                self._h = _scan_begin_ex(reader._h, cols_mask, self._preds, len(preds),
+                                         self._texts, n_texts)
+            else:
+                self._h = _scan_begin(reader._h, cols_mask, self._preds, len(preds))
         if not self._h:
             raise CStripeError("scan_begin: " + errmsg())
         self.reader = reader
@@ -850,6 +934,23 @@ class Scan:
         _check(_last_text_ms(self._h, C.byref(d), C.byref(w), C.byref(t), C.byref(m)),
                "scan_last_text_ms")
         return d.value, w.value, t.value, m.value
+
+    def last_set_ms(self):
+        """(build, probe) device ms of the last stage()'s set work (IN /
+        NOT IN predicates), all sets together; zeros without one"""
+        b, p = C.c_double(), C.c_double()
+        _check(_last_set_ms(self._h, C.byref(b), C.byref(p)), "scan_last_set_ms")
+        return b.value, p.value
+
+    def set_form(self, i):
+        """(form, size) of value set i at the last stage(): form is
+        SET_FORM_NONE (unstaged), SET_FORM_HASH or SET_FORM_BITMAP, size the
+        table's slots or bits"""
+        size = C.c_uint64()
+        rc = _set_form(self._h, i, C.byref(size))
+        if rc < 0:
+            raise CStripeError(f"scan_set_form failed (rc={rc}): {errmsg()}")
+        return rc, size.value
 
     def _decode_ranks(self, col, ranks, nulls):
         """object array of bytes / None from a VARTEXT column's ranks"""

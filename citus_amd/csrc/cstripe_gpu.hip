@@ -206,6 +206,13 @@ struct cs_gpu_state {
      * column's dictionary ranks, parallel to scan->preds (fill_preds) */
     std::vector<uint8_t> tpred_op;
     std::vector<int64_t> tpred_ival;
+    /* IN / NOT IN: one member slot (a projected I8 membership column in
+     * scratch, after the table columns) per distinct (column, set) pair;
+     * mpred_slot is parallel to scan->preds, -1 for every other predicate */
+    struct MemberSlot { uint32_t col, set, proj; };
+    std::vector<MemberSlot> mslots;
+    std::vector<int> mpred_slot;
+    std::vector<void *> set_bufs;    /* set tables (sets_build) */
 };
 
 /* ---------------- error helper ---------------- */
@@ -3231,6 +3238,7 @@ void csgpu_release(cstripe_scan *s)
     if (g->d_tn_emit) HIP_DROP(hipFree(g->d_tn_emit));
     if (g->d_tn_out) HIP_DROP(hipFree(g->d_tn_out));
     if (g->d_tn_perm) HIP_DROP(hipFree(g->d_tn_perm));
+    for (void *b : g->set_bufs) if (b) HIP_DROP(hipFree(b));
     for (hipEvent_t e : g->tev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->hev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->sev) if (e) HIP_DROP(hipEventDestroy(e));
@@ -3241,6 +3249,7 @@ void csgpu_release(cstripe_scan *s)
     #undef HIP_DROP
     delete g;
     s->gpu = nullptr;
+    for (cs_value_set &vs : s->sets) { vs.form = 0; vs.form_size = 0; }
 }
 
 uint64_t csgpu_staged_bytes(const cstripe_scan *s)
@@ -3257,6 +3266,7 @@ struct VtTemps {
     template <typename T>
     hipError_t alloc(T *&p, uint64_t bytes)
     {
+        if (n_bufs >= sizeof(bufs) / sizeof(bufs[0])) return hipErrorOutOfMemory;   /* bufs[] full */
         void *q = nullptr;
         hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
         if (e == hipSuccess) { bufs[n_bufs++] = q; p = (T *)q; }
@@ -3275,6 +3285,7 @@ struct VtTemps {
     }
 };
 static int vartext_build(cstripe_scan *s, VtTemps &vt);
+static int sets_build(cstripe_scan *s, VtTemps &st);
 
 int csgpu_stage(cstripe_scan *s, int device_id)
 {
@@ -3304,6 +3315,30 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         }
     }
     if (n_proj == 0) { cs_set_err("empty projection"); csgpu_release(s); return CSTRIPE_ERR_ARG; }
+    /* member slots of the IN / NOT IN predicates, after the table columns */
+    const uint32_t n_tab = n_proj;
+    g->mpred_slot.assign(s->preds.size(), -1);
+    for (size_t i = 0; i < s->preds.size(); i++) {
+        const cstripe_pred &q = s->preds[i];
+        if (q.op != CSTRIPE_PRED_IN && q.op != CSTRIPE_PRED_NOT_IN) continue;
+        int found = -1;
+        for (size_t m = 0; m < g->mslots.size(); m++)
+            if (g->mslots[m].col == q.column && g->mslots[m].set == (uint32_t)q.ival) found = (int)m;
+        if (found < 0) {
+            if (n_proj >= MAX_PROJ) {
+                cs_set_err("gpu_stage: %u projected columns plus the membership columns of the "
+                           "IN / NOT IN predicates exceed the %d slots of one scan", n_tab, MAX_PROJ);
+                csgpu_release(s);
+                return CSTRIPE_ERR_ARG;
+            }
+            found = (int)g->mslots.size();
+            g->mslots.push_back({q.column, (uint32_t)q.ival, n_proj});
+            g->proj_type[n_proj] = CSTRIPE_I8;
+            n_proj++;
+        }
+        g->mpred_slot[i] = found;
+    }
+    if (!g->mslots.empty()) g->fusable = false;
     g->n_proj = n_proj;
     g->n_groups = (uint32_t)s->sel.size();
 
@@ -3357,9 +3392,14 @@ int csgpu_stage(cstripe_scan *s, int device_id)
             if (nd.n.n_present != nd.n.row_count)
                 rank_words += (rows + 63) / 64;
         }
+        /* membership bytes: n_present entries in a scratch region no decode
+         * segment writes, padded so the probe's dword stores stay inside */
+        for (const auto &ms : g->mslots)
+            scratch_bytes = align_up(scratch_bytes, 16) +
+                            align_up((uint64_t)st.nodes[ms.col][sc.chunk].n.n_present, 16);
     }
     (void)zstd_host;
-    if (any_vartext)
+    if (any_vartext || !g->mslots.empty())
         scratch_bytes += 64;        /* the R-row windowed loads of the dense
                                      * kernels reach up to R-1 entries past a
                                      * rank array's end */
@@ -3617,6 +3657,22 @@ int csgpu_stage(cstripe_scan *s, int device_id)
             }
             h_colloc[(uint64_t)gi * n_proj + pj] = cl;
         }
+        for (const auto &ms : g->mslots) {
+            /* the member column reads like the key column — same exists
+             * bitmap, rank table and dense flag — with one byte per present
+             * value, filled by the probe kernel (sets_build) */
+            const ColLoc &key = h_colloc[(uint64_t)gi * n_proj + g->proj_of_col[ms.col]];
+            ColLoc cl{};
+            cl.type = CSTRIPE_I8;
+            cl.width = 1;
+            cl.exists_off = key.exists_off;
+            cl.rank_off = key.rank_off;
+            cl.flags = (uint16_t)((key.flags & 2) | 1);
+            spos = align_up(spos, 16);
+            cl.val_off = spos;
+            spos += align_up((uint64_t)st.nodes[ms.col][sc.chunk].n.n_present, 16);
+            h_colloc[(uint64_t)gi * n_proj + ms.proj] = cl;
+        }
     }
 
     /* invariant: the layout pass and the fill pass must agree exactly —
@@ -3707,6 +3763,17 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         vt.release();
         if (rc != CSTRIPE_OK) {
             /* the message is set; the scan is left unstaged */
+            csgpu_release(s);
+            s->text_dicts.clear();
+            return rc;
+        }
+    }
+    s->last_set_build_ms = s->last_set_probe_ms = 0;
+    if (!g->mslots.empty()) {
+        VtTemps st;
+        int rc = sets_build(s, st);
+        st.release();
+        if (rc != CSTRIPE_OK) {
             csgpu_release(s);
             s->text_dicts.clear();
             return rc;
@@ -4315,6 +4382,7 @@ static int vartext_build(cstripe_scan *s, VtTemps &vt)
     for (size_t i = 0; i < s->preds.size(); i++) {
         const cstripe_pred &q = s->preds[i];
         if (r->cols[q.column].type != CSTRIPE_VARTEXT) continue;
+        if (g->mpred_slot[i] >= 0) continue;   /* IN / NOT IN: sets_build */
         const cs_text_dict &d = s->text_dicts[q.column];
         const std::string &cst = s->text_consts[(size_t)q.ival];
         const int64_t n = (int64_t)d.offsets.size() - 1;
@@ -4343,6 +4411,346 @@ static int vartext_build(cstripe_scan *s, VtTemps &vt)
         }
         g->tpred_op[i] = op;
         g->tpred_ival[i] = iv;
+    }
+    return CSTRIPE_OK;
+}
+
+/* =====================================================================
+ * Value sets — IN / NOT IN and the device semi-join filter.
+ *
+ * No query kernel knows about sets. At stage each distinct (column, set)
+ * pair is turned into a one-byte MEMBERSHIP column in scratch (a member
+ * slot), so `x IN S` is the integer atom member == 1 and `x NOT IN S` is
+ * member == 0 on every surface — the arrangement VARTEXT uses for ranks.
+ *   build   set_build_kernel: the int64 set (uploaded host copy, VARTEXT
+ *           ranks, or the caller's device array) into a bitmap over
+ *           [lo, hi] (atomicOr on u32 words) or an open-addressing table
+ *           (64-bit atomicCAS claims, multiplicative hash, linear probing;
+ *           the EMPTY pattern is a legal key, kept in a flag word)
+ *   probe   set_probe_kernel: walks each selected chunk's value stream by
+ *           value index through col_value (raw, decoded-in-scratch and
+ *           canonical chunks alike), tests the table — read-only by then —
+ *           with plain loads, and stores four 0/1 bytes per lane
+ * ===================================================================== */
+
+#define SET_EMPTY      (~0ull)
+#define SET_HASH_MUL   0x9E3779B97F4A7C15ull
+#define SET_PROBE_VALS 4u                       /* values per lane */
+#define SET_TILE       (AGG_BLOCK * SET_PROBE_VALS)
+
+struct SetTable {
+    const uint32_t *bits;                 /* bitmap form, else null */
+    const unsigned long long *keys;       /* hash form */
+    const uint32_t *has_empty;            /* hash form: SET_EMPTY is a member */
+    int64_t lo, hi;                       /* bitmap range */
+    uint64_t mask;                        /* hash: slots - 1 */
+    uint32_t shift;                       /* hash: 64 - log2(slots) */
+    uint32_t pad;
+};
+
+__device__ inline uint64_t set_slot(uint64_t key, uint32_t shift)
+{
+    return (key * SET_HASH_MUL) >> shift;
+}
+
+/* [min, max] of a device array: per-lane strided scan, wave shuffle reduce,
+ * one atomic pair per wave on sign-flipped (order-preserving unsigned) words */
+__global__ __launch_bounds__(AGG_BLOCK) void set_range_kernel(
+    const int64_t *__restrict__ vals, uint64_t n, unsigned long long *out)
+{
+    int64_t mn = INT64_MAX, mx = INT64_MIN;
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const int64_t v = vals[i];
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        const int64_t a = __shfl_down(mn, off, WAVE), b = __shfl_down(mx, off, WAVE);
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+    }
+    if (threadIdx.x % WAVE == 0) {
+        atomicMin(&out[0], (unsigned long long)mn ^ 0x8000000000000000ull);
+        atomicMax(&out[1], (unsigned long long)mx ^ 0x8000000000000000ull);
+    }
+}
+
+int csgpu_set_range(const int64_t *dev_vals, uint64_t n, int64_t *lo, int64_t *hi, int *dev_id)
+{
+    if (!cstripe_gpu_available()) { cs_set_err("scan_begin_sets: a device set needs a visible MI355X"); return CSTRIPE_ERR_NOGPU; }
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, dev_vals) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        cs_set_err("scan_begin_sets: on_device set values are not a device pointer");
+        return CSTRIPE_ERR_ARG;
+    }
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    HIP_TRY(hipSetDevice(at.device));
+    *dev_id = at.device;
+    unsigned long long *d_out = nullptr;
+    unsigned long long h_out[2] = {~0ull, 0ull};
+    int rc = CSTRIPE_OK;
+    auto fail = [&](hipError_t e, const char *what) {
+        if (e == hipSuccess || rc != CSTRIPE_OK) return;
+        cs_set_err("scan_begin_sets: %s failed: %s", what, hipGetErrorString(e));
+        rc = CSTRIPE_ERR;
+    };
+    fail(hipMalloc(&d_out, sizeof(h_out)), "hipMalloc");
+    if (rc == CSTRIPE_OK) {
+        fail(hipMemcpy(d_out, h_out, sizeof(h_out), hipMemcpyHostToDevice), "hipMemcpy");
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + AGG_BLOCK - 1) / AGG_BLOCK, 1024);
+        if (rc == CSTRIPE_OK) {
+            hipLaunchKernelGGL(set_range_kernel, dim3(grid), dim3(AGG_BLOCK), 0, 0, dev_vals, n, d_out);
+            fail(hipGetLastError(), "set_range_kernel");
+            fail(hipMemcpy(h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        (void)hipFree(d_out);
+    }
+    (void)hipSetDevice(prev);
+    if (rc != CSTRIPE_OK) return rc;
+    *lo = (int64_t)(h_out[0] ^ 0x8000000000000000ull);
+    *hi = (int64_t)(h_out[1] ^ 0x8000000000000000ull);
+    return CSTRIPE_OK;
+}
+
+/* insert vals[0..n) into the table. bits != null: bitmap over [lo, hi] (a
+ * value outside it — a device set that changed since begin — is dropped, the
+ * index never leaves the allocation). Else hash: slots >= 2n, so a probe
+ * sequence always meets its key or an EMPTY slot. */
+__global__ __launch_bounds__(AGG_BLOCK) void set_build_kernel(
+    const int64_t *__restrict__ vals, uint64_t n, uint32_t *bits,
+    unsigned long long *keys, uint32_t *has_empty, SetTable t)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const int64_t v = vals[i];
+        if (bits) {
+            if (v < t.lo || v > t.hi) continue;
+            const uint64_t d = (uint64_t)v - (uint64_t)t.lo;
+            atomicOr(&bits[d >> 5], 1u << (d & 31u));
+            continue;
+        }
+        const unsigned long long key = (unsigned long long)v;
+        if (key == SET_EMPTY) { atomicOr(has_empty, 1u); continue; }
+        uint64_t h = set_slot(key, t.shift);
+        for (uint64_t tries = 0; tries <= t.mask; tries++) {
+            const unsigned long long prev = atomicCAS(&keys[h], SET_EMPTY, key);
+            if (prev == SET_EMPTY || prev == key) break;
+            h = (h + 1) & t.mask;
+        }
+    }
+}
+
+__device__ inline uint32_t set_test(const SetTable &t, int64_t v)
+{
+    if (t.bits) {
+        if (v < t.lo || v > t.hi) return 0;
+        const uint64_t d = (uint64_t)v - (uint64_t)t.lo;
+        return (t.bits[d >> 5] >> (d & 31u)) & 1u;
+    }
+    const unsigned long long key = (unsigned long long)v;
+    if (key == SET_EMPTY) return *t.has_empty & 1u;
+    uint64_t h = set_slot(key, t.shift);
+    for (uint64_t tries = 0; tries <= t.mask; tries++) {
+        const unsigned long long k = t.keys[h];
+        if (k == key) return 1;
+        if (k == SET_EMPTY) return 0;
+        h = (h + 1) & t.mask;
+    }
+    return 0;
+}
+
+/* one block per (chunk group, tile of SET_TILE values); lane: four
+ * consecutive value indexes, one dword of 0/1 bytes. The member region is
+ * padded to 16 bytes, so the tail dword stays inside it. */
+__global__ __launch_bounds__(AGG_BLOCK) void set_probe_kernel(
+    const uint8_t *__restrict__ data, uint8_t *scratch,
+    const ColLoc *__restrict__ colloc, const uint32_t *__restrict__ n_present,
+    uint32_t n_proj, uint32_t key_proj, uint32_t member_proj, uint32_t tiles_pg,
+    SetTable t)
+{
+    const uint32_t gi = blockIdx.x / tiles_pg, tile = blockIdx.x % tiles_pg;
+    const uint32_t np = n_present[gi];
+    const uint32_t v0 = (tile * AGG_BLOCK + threadIdx.x) * SET_PROBE_VALS;
+    if (v0 >= np) return;
+    ColLoc key = colloc[(uint64_t)gi * n_proj + key_proj];
+    key.flags |= 2;                       /* by value index: no exists bitmap */
+    const uint64_t out_off = colloc[(uint64_t)gi * n_proj + member_proj].val_off;
+    uint32_t word = 0;
+    #pragma unroll
+    for (uint32_t k = 0; k < SET_PROBE_VALS; k++) {
+        if (v0 + k >= np) break;
+        int64_t iv = 0;
+        double fv = 0;
+        col_value(data, scratch, nullptr, key, v0 + k, iv, fv);
+        word |= set_test(t, iv) << (8u * k);
+    }
+    *(uint32_t *)(scratch + out_off + v0) = word;
+}
+
+static int sets_build(cstripe_scan *s, VtTemps &st)
+{
+    cs_gpu_state *g = s->gpu;
+    cstripe_reader *r = s->r;
+    const uint32_t n_proj = g->n_proj;
+    int force = 0;                         /* CSTRIPE_SET_FORM_*, 0 = choose */
+    if (const char *e = getenv("CSTRIPE_SET_FORM")) {
+        if (!strcmp(e, "hash")) force = CSTRIPE_SET_FORM_HASH;
+        else if (!strcmp(e, "bitmap")) force = CSTRIPE_SET_FORM_BITMAP;
+    }
+    for (hipEvent_t &e : st.ev) HIP_TRY(hipEventCreate(&e));
+
+    /* the key columns must be readable: decode what lands in scratch, once.
+     * Every query call decodes the same segments again (no decoded flag is
+     * shared with them; redundant, harmless). The membership regions survive
+     * those decodes because a decode kernel stores only inside its segment's
+     * own 16-byte-padded region, never past it — what the VARTEXT rank
+     * regions rely on too. */
+    bool need_decode = false;
+    for (const auto &ms : g->mslots)
+        if (g->col_scratch[(size_t)g->proj_of_col[ms.col]]) need_decode = true;
+    if (need_decode) {
+        HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+        { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+        int h_err = 0;
+        HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    }
+
+    uint32_t tiles_pg = (g->max_group_rows + SET_TILE - 1) / SET_TILE;
+    if (tiles_pg == 0) tiles_pg = 1;
+    if ((uint64_t)g->n_groups * tiles_pg >= (1ull << 31)) { cs_set_err("gpu_stage: too many tiles for the set probe"); return CSTRIPE_ERR_ARG; }
+
+    struct Built { bool ok = false; SetTable t{}; };
+    std::vector<Built> per_set(s->sets.size());
+    std::vector<uint32_t> h_np(g->n_groups);
+    uint32_t *d_np = nullptr;
+    HIP_TRY(st.alloc(d_np, (uint64_t)g->n_groups * sizeof(uint32_t)));
+    float ms_f = 0;
+
+    for (const auto &ms : g->mslots) {
+        cs_value_set &vs = s->sets[ms.set];
+        const bool vartext = r->cols[ms.col].type == CSTRIPE_VARTEXT;
+        Built local;
+        Built &b = vartext ? local : per_set[ms.set];   /* ranks are per column */
+        if (!b.ok) {
+            /* ---- the int64 entries and their range ---- */
+            std::vector<int64_t> ranks;
+            const std::vector<int64_t> *hv = &vs.vals;
+            if (vartext) {
+                const cs_text_dict &d = s->text_dicts[ms.col];
+                const int64_t nd = (int64_t)d.offsets.size() - 1;
+                for (const std::string &tx : vs.texts) {
+                    int64_t lo = 0, hi = nd;
+                    while (lo < hi) {
+                        const int64_t mid = (lo + hi) / 2;
+                        if (vt_cmp(d.bytes.data() + d.offsets[mid], d.offsets[mid + 1] - d.offsets[mid],
+                                   (const uint8_t *)tx.data(), tx.size()) < 0) lo = mid + 1; else hi = mid;
+                    }
+                    if (lo < nd && vt_cmp(d.bytes.data() + d.offsets[lo], d.offsets[lo + 1] - d.offsets[lo],
+                                          (const uint8_t *)tx.data(), tx.size()) == 0)
+                        ranks.push_back(lo);
+                }
+                std::sort(ranks.begin(), ranks.end());
+                ranks.erase(std::unique(ranks.begin(), ranks.end()), ranks.end());
+                hv = &ranks;
+            }
+            uint64_t n = vs.on_device ? vs.n : hv->size();
+            int64_t lo = 0, hi = 0;
+            if (n) {
+                lo = vs.on_device ? vs.lo : hv->front();
+                hi = vs.on_device ? vs.hi : hv->back();
+            }
+            if (vs.on_device && n && vs.dev_id != g->device) {
+                cs_set_err("gpu_stage: set %u lives on device %d, the scan is staged on device %d",
+                           ms.set, vs.dev_id, g->device);
+                return CSTRIPE_ERR_ARG;
+            }
+            /* ---- form ---- */
+            const uint64_t span = (uint64_t)hi - (uint64_t)lo;         /* hi - lo, exact */
+            const bool bitmap_legal = span < (1ull << 32);
+            const uint64_t want = std::max<uint64_t>(1ull << 16, 128 * n);
+            int form = (bitmap_legal && span + 1 <= want) ? CSTRIPE_SET_FORM_BITMAP
+                                                          : CSTRIPE_SET_FORM_HASH;
+            if (force == CSTRIPE_SET_FORM_HASH) form = force;
+            if (force == CSTRIPE_SET_FORM_BITMAP && bitmap_legal) form = force;
+            /* ---- table ---- */
+            const int64_t *d_vals = vs.on_device ? vs.dev_vals : nullptr;
+            if (!vs.on_device && n) {
+                int64_t *up = nullptr;
+                HIP_TRY(st.alloc(up, n * sizeof(int64_t)));
+                HIP_TRY(hipMemcpyAsync(up, hv->data(), n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+                d_vals = up;
+            }
+            uint32_t *d_bits = nullptr, *d_flag = nullptr;
+            unsigned long long *d_keys = nullptr;
+            SetTable t{};
+            t.lo = lo;
+            t.hi = hi;
+            uint64_t size;
+            /* build time = clearing the table + the insert kernel (the host
+             * set's upload above is not in it) */
+            HIP_TRY(hipEventRecord(st.ev[0], g->stream));
+            if (form == CSTRIPE_SET_FORM_BITMAP) {
+                size = span + 1;
+                const uint64_t words = (size + 31) / 32;
+                void *q = nullptr;
+                HIP_TRY(hipMalloc(&q, words * 4));
+                g->set_bufs.push_back(q);
+                d_bits = (uint32_t *)q;
+                HIP_TRY(hipMemsetAsync(d_bits, 0, words * 4, g->stream));
+            } else {
+                uint64_t slots = 2;
+                uint32_t lg = 1;
+                while (slots < 2 * n) { slots <<= 1; lg++; }
+                size = slots;
+                void *q = nullptr;
+                HIP_TRY(hipMalloc(&q, slots * 8 + 8));
+                g->set_bufs.push_back(q);
+                d_keys = (unsigned long long *)q;
+                d_flag = (uint32_t *)(d_keys + slots);
+                HIP_TRY(hipMemsetAsync(d_keys, 0xFF, slots * 8, g->stream));
+                HIP_TRY(hipMemsetAsync(d_flag, 0, 8, g->stream));
+                t.mask = slots - 1;
+                t.shift = 64 - lg;
+            }
+            if (n) {
+                const uint32_t grid = (uint32_t)std::min<uint64_t>((n + AGG_BLOCK - 1) / AGG_BLOCK, 4096);
+                hipLaunchKernelGGL(set_build_kernel, dim3(grid), dim3(AGG_BLOCK), 0, g->stream,
+                                   d_vals, n, d_bits, d_keys, d_flag, t);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipEventRecord(st.ev[1], g->stream));
+            HIP_TRY(hipStreamSynchronize(g->stream));
+            (void)hipEventElapsedTime(&ms_f, st.ev[0], st.ev[1]);
+            s->last_set_build_ms += ms_f;
+            t.bits = d_bits;
+            t.keys = d_keys;
+            t.has_empty = d_flag;
+            b.t = t;
+            b.ok = true;
+            vs.form = form;
+            vs.form_size = size;
+        }
+        /* ---- probe (an empty selection still reports the set's form) ---- */
+        if (g->n_groups == 0) continue;
+        for (uint32_t gi = 0; gi < g->n_groups; gi++) {
+            const cs_selchunk &sc = s->sel[gi];
+            h_np[gi] = r->stripes[sc.stripe].nodes[ms.col][sc.chunk].n.n_present;
+        }
+        HIP_TRY(hipMemcpyAsync(d_np, h_np.data(), h_np.size() * sizeof(uint32_t), hipMemcpyHostToDevice, g->stream));
+        HIP_TRY(hipEventRecord(st.ev[2], g->stream));
+        hipLaunchKernelGGL(set_probe_kernel, dim3(g->n_groups * tiles_pg), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_data, g->d_scratch, g->d_colloc, d_np, n_proj,
+                           (uint32_t)g->proj_of_col[ms.col], ms.proj, tiles_pg, b.t);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(st.ev[3], g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));   /* h_np is reused */
+        (void)hipEventElapsedTime(&ms_f, st.ev[2], st.ev[3]);
+        s->last_set_probe_ms += ms_f;
     }
     return CSTRIPE_OK;
 }
@@ -4386,6 +4794,14 @@ static void fill_preds(const cstripe_scan *s, AggParams &p)
         if (t == CSTRIPE_VARTEXT) {
             p.preds[i].op = g->tpred_op[i];
             p.preds[i].ival = g->tpred_ival[i];
+            p.preds[i].fval = 0.0;
+        }
+        if (g->mpred_slot[i] >= 0) {
+            /* IN / NOT IN: one integer atom over the membership column */
+            p.preds[i].proj = (uint16_t)g->mslots[(size_t)g->mpred_slot[i]].proj;
+            p.preds[i].op = CSTRIPE_PRED_EQ;
+            p.preds[i].is_float = 0;
+            p.preds[i].ival = q.op == CSTRIPE_PRED_IN ? 1 : 0;
             p.preds[i].fval = 0.0;
         }
     }

@@ -1303,19 +1303,96 @@ extern "C" cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_
                                                const cstripe_text_const *text_consts,
                                                uint32_t n_text_consts)
 {
+    return cstripe_scan_begin_sets(r, cols_mask, preds, n_preds, text_consts, n_text_consts,
+                                   nullptr, 0);
+}
+
+static inline bool pred_is_set(const cstripe_pred &p)
+{
+    return p.op == CSTRIPE_PRED_IN || p.op == CSTRIPE_PRED_NOT_IN;
+}
+
+/* IN over a sorted key list: true when no key lies in [min, max] */
+static bool set_refutes(const std::vector<int64_t> &keys, int64_t min_i, int64_t max_i)
+{
+    auto it = std::lower_bound(keys.begin(), keys.end(), min_i);
+    return it == keys.end() || *it > max_i;
+}
+
+extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t cols_mask,
+                                                 const cstripe_pred *preds, uint32_t n_preds,
+                                                 const cstripe_text_const *text_consts,
+                                                 uint32_t n_text_consts,
+                                                 const cstripe_value_set *sets, uint32_t n_sets)
+{
     if (!r) { cs_set_err("scan_begin: null reader"); return nullptr; }
     auto *s = new cstripe_scan();
     s->r = r;
     s->cols_mask = cols_mask;
     if (n_preds > CSTRIPE_MAX_PREDS) { cs_set_err("too many predicates (max %d)", CSTRIPE_MAX_PREDS); delete s; return nullptr; }
+    if (n_sets > CSTRIPE_MAX_SETS) { cs_set_err("scan_begin_sets: %u value sets (max %d)", n_sets, CSTRIPE_MAX_SETS); delete s; return nullptr; }
+    if (n_sets && !sets) { cs_set_err("scan_begin_sets: %u value sets but no array", n_sets); delete s; return nullptr; }
     for (uint32_t i = 0; i < n_text_consts; i++) {
         if (!text_consts || (!text_consts[i].data && text_consts[i].len)) { cs_set_err("scan_begin: text constant %u has no data", i); delete s; return nullptr; }
         s->text_consts.emplace_back((const char *)text_consts[i].data, text_consts[i].len);
     }
+    /* the sets: host entries are copied here (integers sorted and
+     * deduplicated: the copy chunk refutation searches and the stage
+     * uploads); a device set is reduced to its [min, max] */
+    s->sets.resize(n_sets);
+    for (uint32_t i = 0; i < n_sets; i++) {
+        const cstripe_value_set &in = sets[i];
+        cs_value_set &vs = s->sets[i];
+        if (in.n > CSTRIPE_MAX_SET_VALUES) {
+            cs_set_err("scan_begin_sets: set %u holds %llu values (max %llu)", i,
+                       (unsigned long long)in.n, (unsigned long long)CSTRIPE_MAX_SET_VALUES);
+            delete s; return nullptr;
+        }
+        if (in.values && in.texts) { cs_set_err("scan_begin_sets: set %u gives both values and texts", i); delete s; return nullptr; }
+        if (in.n && !in.values && !in.texts) { cs_set_err("scan_begin_sets: set %u has %llu entries but no data", i, (unsigned long long)in.n); delete s; return nullptr; }
+        vs.n = in.n;
+        vs.is_text = in.texts != nullptr;
+        vs.on_device = in.on_device != 0 && in.values != nullptr;
+        if (in.on_device && in.texts) { cs_set_err("scan_begin_sets: set %u: device sets are int64 only", i); delete s; return nullptr; }
+        if (vs.is_text) {
+            for (uint64_t k = 0; k < in.n; k++) {
+                if (!in.texts[k].data && in.texts[k].len) { cs_set_err("scan_begin_sets: set %u text %llu has no data", i, (unsigned long long)k); delete s; return nullptr; }
+                vs.texts.emplace_back((const char *)in.texts[k].data, in.texts[k].len);
+            }
+        } else if (vs.on_device) {
+            vs.dev_vals = in.values;
+            if (in.n && csgpu_set_range(in.values, in.n, &vs.lo, &vs.hi, &vs.dev_id) != CSTRIPE_OK) { delete s; return nullptr; }
+        } else if (in.n) {
+            vs.vals.assign(in.values, in.values + in.n);
+            std::sort(vs.vals.begin(), vs.vals.end());
+            vs.vals.erase(std::unique(vs.vals.begin(), vs.vals.end()), vs.vals.end());
+        }
+    }
     for (uint32_t i = 0; i < n_preds; i++) {
         if (preds[i].column >= r->cols.size()) { cs_set_err("pred column out of range"); delete s; return nullptr; }
-        if (r->cols[preds[i].column].type == CSTRIPE_VARTEXT &&
-            (preds[i].ival < 0 || (uint64_t)preds[i].ival >= n_text_consts)) {
+        if (preds[i].op > CSTRIPE_PRED_NOT_IN) { cs_set_err("scan_begin: predicate %u has unknown op %u", i, preds[i].op); delete s; return nullptr; }
+        if (pred_is_set(preds[i])) {
+            const uint8_t t = r->cols[preds[i].column].type;
+            if (preds[i].ival < 0 || (uint64_t)preds[i].ival >= n_sets) {
+                cs_set_err("scan_begin: predicate %u is IN / NOT IN: ival %lld is not an index "
+                           "into the %u value sets (cstripe_scan_begin_sets)", i,
+                           (long long)preds[i].ival, n_sets);
+                delete s; return nullptr;
+            }
+            const cs_value_set &vs = s->sets[(size_t)preds[i].ival];
+            if (t == CSTRIPE_F32 || t == CSTRIPE_F64) {
+                cs_set_err("scan_begin_sets: predicate %u: IN / NOT IN over float column %u is not supported", i, preds[i].column);
+                delete s; return nullptr;
+            }
+            if (t == CSTRIPE_VARTEXT ? (!vs.is_text && (vs.on_device || sets[preds[i].ival].values))
+                                     : vs.is_text) {
+                cs_set_err("scan_begin_sets: predicate %u: set %lld gives %s but column %u is %s",
+                           i, (long long)preds[i].ival, vs.is_text ? "texts" : "values",
+                           preds[i].column, t == CSTRIPE_VARTEXT ? "VARTEXT" : "not VARTEXT");
+                delete s; return nullptr;
+            }
+        } else if (r->cols[preds[i].column].type == CSTRIPE_VARTEXT &&
+                   (preds[i].ival < 0 || (uint64_t)preds[i].ival >= n_text_consts)) {
             cs_set_err("scan_begin: predicate %u on VARTEXT column %u needs a string "
                        "constant: ival %lld is not an index into the %u text constants "
                        "(cstripe_scan_begin_ex)", i, preds[i].column,
@@ -1337,6 +1414,24 @@ extern "C" cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_
                      });
     if (s->cols_mask == 0)
         s->cols_mask = 1;   /* pure count(*): still scan one column's chunks */
+    /* chunk-refutation keys of the TEXT / VARTEXT set predicates */
+    s->set_keys.resize(s->preds.size());
+    bool any_set = false;
+    for (size_t i = 0; i < s->preds.size(); i++) {
+        const cstripe_pred &p = s->preds[i];
+        if (!pred_is_set(p)) continue;
+        any_set = true;
+        const cs_value_set &vs = s->sets[(size_t)p.ival];
+        const uint8_t t = r->cols[p.column].type;
+        if (p.op != CSTRIPE_PRED_IN || vs.on_device) continue;
+        std::vector<int64_t> &keys = s->set_keys[i];
+        if (t == CSTRIPE_TEXT)
+            for (int64_t v : vs.vals) keys.push_back(csf_text_lex_key((uint32_t)v));
+        else if (t == CSTRIPE_VARTEXT)
+            for (const std::string &tx : vs.texts)
+                keys.push_back(csvt_prefix_key((const uint8_t *)tx.data(), (uint32_t)tx.size()));
+        std::sort(keys.begin(), keys.end());
+    }
     /* device pruning (SelectedChunkMask on GPU): same CNF
      * refutation evaluated one-thread-per-chunk; worthwhile when the
      * footer directory holds many thousands of chunk groups. Identical
@@ -1352,6 +1447,7 @@ extern "C" cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_
         for (const auto &p : s->preds)
             any_text |= r->cols[p.column].type == CSTRIPE_TEXT ||
                         r->cols[p.column].type == CSTRIPE_VARTEXT;
+        any_text |= any_set;     /* nor about value sets */
         std::vector<uint8_t> selmask;
         if (!s->preds.empty() && !any_text && dpv != 0 &&
             (dpv == 1 || total_chunks >= 8192) &&
@@ -1388,6 +1484,29 @@ extern "C" cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_
                     /* all-NULL chunks have no min/max and are never refuted
                      * (columnar_reader.c:1160-1166) */
                     int64_t text_key = 0;
+                    if (pred_is_set(p)) {
+                        /* IN: no set element in [min, max] (a device set is
+                         * known by its range only); NOT IN never refutes */
+                        const cs_value_set &vs = s->sets[(size_t)p.ival];
+                        const uint8_t t = r->cols[p.column].type;
+                        bool refuted = false;
+                        if (p.op == CSTRIPE_PRED_IN && nd.has_min_max) {
+                            /* a device set's range is over raw values: TEXT
+                             * min/max are lex keys, not slots, so there only
+                             * the empty set refutes */
+                            if (vs.on_device)
+                                refuted = vs.n == 0 ||
+                                          (t != CSTRIPE_TEXT &&
+                                           (vs.hi < nd.min_i || vs.lo > nd.max_i));
+                            else
+                                refuted = set_refutes(t == CSTRIPE_TEXT || t == CSTRIPE_VARTEXT
+                                                          ? s->set_keys[j] : vs.vals,
+                                                      nd.min_i, nd.max_i);
+                        }
+                        if (!refuted) group_refuted = false;
+                        j++;
+                        continue;
+                    }
                     if (r->cols[p.column].type == CSTRIPE_VARTEXT) {
                         const std::string &tc = s->text_consts[(size_t)p.ival];
                         text_key = csvt_prefix_key((const uint8_t *)tc.data(), (uint32_t)tc.size());
@@ -1457,6 +1576,22 @@ extern "C" int cstripe_scan_text_dict(const cstripe_scan *s, uint32_t col, uint3
     *offsets = d.offsets.data();
     *bytes = d.bytes.data();
     return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_last_set_ms(const cstripe_scan *s, double *build_ms, double *probe_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (build_ms) *build_ms = s->last_set_build_ms;
+    if (probe_ms) *probe_ms = s->last_set_probe_ms;
+    return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_set_form(const cstripe_scan *s, uint32_t set_idx, uint64_t *size)
+{
+    if (!s || set_idx >= s->sets.size()) { cs_set_err("scan_set_form: set %u is not a set of this scan", set_idx); return CSTRIPE_ERR_ARG; }
+    const bool staged = s->gpu != nullptr;
+    if (size) *size = staged ? s->sets[set_idx].form_size : 0;
+    return staged ? s->sets[set_idx].form : CSTRIPE_SET_FORM_NONE;
 }
 
 extern "C" int cstripe_scan_last_text_ms(const cstripe_scan *s, double *decode_ms,

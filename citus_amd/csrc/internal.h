@@ -63,10 +63,30 @@ struct cs_text_dict {
     std::vector<uint8_t> bytes;      /* entries in memcmp order */
 };
 
+/* one value set of IN / NOT_IN predicates (cstripe_scan_begin_sets) */
+struct cs_value_set {
+    std::vector<int64_t> vals;        /* host integer set: sorted, deduplicated */
+    std::vector<std::string> texts;   /* host VARTEXT set, as given */
+    bool is_text = false;
+    bool on_device = false;
+    const int64_t *dev_vals = nullptr;   /* device set: the caller's pointer */
+    uint64_t n = 0;                      /* entries as given */
+    int dev_id = -1;                     /* device that owns dev_vals */
+    int64_t lo = 0, hi = 0;              /* device set: [min, max], n > 0 */
+    int form = 0;                        /* CSTRIPE_SET_FORM_* at the last stage */
+    uint64_t form_size = 0;              /* slots or bits */
+};
+
 struct cstripe_scan {
     cstripe_reader *r = nullptr;
     uint64_t cols_mask = 0;
     std::vector<cstripe_pred> preds;
+    std::vector<cs_value_set> sets;         /* IN / NOT_IN preds: ival indexes these */
+    /* [pred]: sorted chunk-refutation keys of a TEXT (lex keys) or VARTEXT
+     * (prefix keys) set predicate; integer columns use sets[].vals */
+    std::vector<std::vector<int64_t>> set_keys;
+    double last_set_build_ms = 0.0;         /* stage-time set split */
+    double last_set_probe_ms = 0.0;
     std::vector<std::string> text_consts;   /* VARTEXT preds: ival indexes these */
     std::vector<cs_text_dict> text_dicts;   /* [column]; built at stage */
     double last_text_decode_ms = 0.0;       /* stage-time VARTEXT split */
@@ -108,6 +128,10 @@ struct cstripe_scan {
  * host loop). preds must be normalized + group-sorted (scan_begin's form). */
 int  csgpu_prune(cstripe_reader *r, const std::vector<cstripe_pred> &preds,
                  std::vector<uint8_t> &selected);
+/* [min, max] of a device-resident int64 array (one reduction kernel on the
+ * device that owns the pointer, reported in *dev_id); n > 0 */
+int  csgpu_set_range(const int64_t *dev_vals, uint64_t n, int64_t *lo, int64_t *hi,
+                     int *dev_id);
 int  csgpu_stage(cstripe_scan *s, int device_id);
 void csgpu_release(cstripe_scan *s);
 uint64_t csgpu_staged_bytes(const cstripe_scan *s);

@@ -57,6 +57,9 @@ extern "C" {
 /* capacity limits of one scan */
 #define CSTRIPE_MAX_PREDS 16
 #define CSTRIPE_MAX_AGGS  12
+/* value sets of one scan (cstripe_scan_begin_sets), and entries of one set */
+#define CSTRIPE_MAX_SETS        4
+#define CSTRIPE_MAX_SET_VALUES  (1ull << 26)
 
 /* ---- error codes ---- */
 #define CSTRIPE_OK            0
@@ -201,10 +204,17 @@ void cstripe_default_options(cstripe_options *opts);
  * reference leaving such clauses to ExecQual. Values are given in the
  * column's physical representation (i64 for integer/fixed-point/date
  * columns, f64 for floats). NULL operands fail the atom (SQL semantics at
- * the top-level filter). */
+ * the top-level filter).
+ *
+ * IN / NOT_IN are the set-membership atoms — `col = ANY(array)`, the
+ * ScalarArrayOpExpr the reference pushes into the scan whole, at any list
+ * length (columnar_customscan.c:840-850), and `col <> ALL(array)`. Their
+ * ival is an INDEX into the value sets of cstripe_scan_begin_sets; one atom
+ * whatever the set's size, so a long list does not eat CSTRIPE_MAX_PREDS. */
 typedef enum cstripe_predop {
     CSTRIPE_PRED_LT = 0, CSTRIPE_PRED_LE, CSTRIPE_PRED_GT, CSTRIPE_PRED_GE,
     CSTRIPE_PRED_EQ, CSTRIPE_PRED_NE,
+    CSTRIPE_PRED_IN = 6, CSTRIPE_PRED_NOT_IN = 7,
 } cstripe_predop;
 
 typedef struct cstripe_pred {
@@ -215,6 +225,16 @@ typedef struct cstripe_pred {
     uint32_t    or_group;  /* 0 = standalone conjunct; same nonzero id = OR'd */
     uint32_t    _pad;
 } cstripe_pred;
+
+/* a value set of IN / NOT_IN predicates (cstripe_scan_begin_sets). A set
+ * holds no NULLs; duplicates are allowed. */
+typedef struct cstripe_value_set {
+    const int64_t            *values;   /* n entries; host memory, or device memory when on_device */
+    const cstripe_text_const *texts;    /* n entries, host; for a VARTEXT column (values NULL) */
+    uint64_t                  n;        /* 0 is legal */
+    uint32_t                  on_device;
+    uint32_t                  _pad;
+} cstripe_value_set;
 
 /* ---- aggregates ----
  * The worker-partial shapes of the built-ins on the hot path
@@ -389,6 +409,74 @@ cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_mask,
                                     const cstripe_pred *preds, uint32_t n_preds,
                                     const cstripe_text_const *text_consts,
                                     uint32_t n_text_consts);
+/* scan_begin_sets: scan_begin_ex plus value sets for IN / NOT_IN atoms. With
+ * n_sets == 0 it is exactly cstripe_scan_begin_ex (which calls it).
+ *  - For op IN / NOT_IN, ival is an INDEX into sets — for every column type,
+ *    VARTEXT included; fval is ignored. Several predicates may name one set.
+ *    cstripe_scan_begin and cstripe_scan_begin_ex have no sets and fail on
+ *    either op, naming this entry.
+ *  - Key column types: I8/I16/I32/I64 — set values are int64, a value outside
+ *    the column's range simply never matches; TEXT — values are whole 4-byte
+ *    slots zero-extended, as for EQ; VARTEXT — the set gives `texts` (values
+ *    NULL): at stage each string is looked up in the column's per-scan
+ *    dictionary, absent strings drop out and the set becomes a set of ranks.
+ *    An F32/F64 key column returns NULL with a message.
+ *  - Memory: host values / texts are copied at begin. A device set
+ *    (on_device != 0, int64 only) is read in place: the pointer must stay
+ *    valid and unchanged until cstripe_scan_end, because every stage rebuilds
+ *    from it. It must live on the device the scan is staged on.
+ *  - Row semantics, as in SQL: x IN S passes iff x is non-NULL and in S;
+ *    x NOT IN S passes iff x is non-NULL and not in S; a NULL operand fails
+ *    either atom. The empty set gives IN -> no row, NOT IN -> every non-NULL
+ *    row. Both are ordinary atoms, usable inside an or_group.
+ *  - Errors (NULL, message set): a set index >= n_sets, n_sets >
+ *    CSTRIPE_MAX_SETS, n > CSTRIPE_MAX_SET_VALUES, texts on a non-VARTEXT
+ *    column or values on a VARTEXT column, a device text set, an op above 7.
+ *  - Chunk refutation (host side; the device prune kernel is skipped when a
+ *    set predicate is present, as for TEXT): IN refutes a chunk that has
+ *    min/max iff no set element lies in [min, max] — over the values for
+ *    integer columns, over the C-collation lex keys of the slots for TEXT,
+ *    over the 7-byte prefix keys for VARTEXT (inclusive bounds, so an element
+ *    sharing its prefix with a chunk boundary keeps that chunk). For a device
+ *    set one reduction kernel at begin yields the set's [min, max] and
+ *    nothing else; IN then refutes only when that range misses the chunk's.
+ *    On a TEXT column a device set never refutes (unless empty): its range
+ *    is over slot values, the skip nodes hold lex keys.
+ *    NOT_IN never refutes. All-NULL chunks (no min/max) survive.
+ *  - Device evaluation: all at cstripe_gpu_stage, no query kernel knows about
+ *    sets. Each distinct (column, set) pair gets one extra projected slot — a
+ *    one-byte MEMBERSHIP column in scratch, sharing the key column's exists
+ *    bitmap. A build kernel turns the set into a bitmap over [lo, hi] (when
+ *    hi - lo + 1 <= max(2^16, 128 n) and <= 2^32) or an open-addressing hash
+ *    table of max(2, next_pow2(2 n)) 64-bit slots; a probe kernel walks the
+ *    key column's value streams once and writes 0/1 bytes. IN is then the
+ *    integer atom member == 1, NOT_IN member == 0, on every surface
+ *    (scan_agg and its grouped / hashed forms, scan_select, select_topn).
+ *    Such scans never take the fused or overlapped aggregate bodies
+ *    (cstripe_scan_last_agg_path reports DENSE or GENERAL). The slots count
+ *    against the 16 projected columns of one scan; overflow is
+ *    CSTRIPE_ERR_ARG from cstripe_gpu_stage and leaves the scan unstaged.
+ *  - CSTRIPE_SET_FORM=hash|bitmap (environment, read per stage) forces the
+ *    form; a forced bitmap over a range beyond 2^32 falls back to hash.
+ *    Results never depend on it. */
+cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t cols_mask,
+                                      const cstripe_pred *preds, uint32_t n_preds,
+                                      const cstripe_text_const *text_consts,
+                                      uint32_t n_text_consts,
+                                      const cstripe_value_set *sets, uint32_t n_sets);
+/* device time (hipEvents, milliseconds) of the last cstripe_gpu_stage's set
+ * work, all sets together: table build (clearing the table + the insert
+ * kernel; a host set's upload is not in it), membership probe. Both 0 when
+ * the scan has no set predicate. Any out pointer may be NULL. */
+int cstripe_scan_last_set_ms(const cstripe_scan *s, double *build_ms, double *probe_ms);
+/* form chosen for set set_idx at the last stage: 0 none / unstaged / unused,
+ * 1 hash, 2 bitmap; *size (may be NULL) gets the table's slots or bits. A
+ * set used on several VARTEXT columns reports the last table built from it.
+ * CSTRIPE_ERR_ARG when set_idx is not a set of this scan. */
+#define CSTRIPE_SET_FORM_NONE   0
+#define CSTRIPE_SET_FORM_HASH   1
+#define CSTRIPE_SET_FORM_BITMAP 2
+int cstripe_scan_set_form(const cstripe_scan *s, uint32_t set_idx, uint64_t *size);
 void cstripe_scan_end(cstripe_scan *s);
 int64_t cstripe_scan_chunk_groups_filtered(const cstripe_scan *s);
 
