@@ -90,6 +90,87 @@ class ValueSet(C.Structure):
                 ("n", C.c_uint64), ("on_device", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+MAX_LOOKUPS = 2
+MAX_LOOKUP_PAYLOADS = 4
+LOOKUP_INNER = 1
+LOOKUP_FORM_NONE, LOOKUP_FORM_HASH, LOOKUP_FORM_DIRECT = 0, 1, 2
+
+
+class LookupIn(C.Structure):
+    """cstripe_lookup"""
+    _fields_ = [("key_column", C.c_uint32), ("n_payloads", C.c_uint32),
+                ("keys", C.c_void_p),
+                ("payloads", C.c_void_p * MAX_LOOKUP_PAYLOADS),
+                ("n", C.c_uint64), ("on_device", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Lookup:
+    """The build side of an N:1 join for Reader.scan(lookups=[...]): the
+    scanned table's `key_col` is looked up in `keys` (distinct, no NULLs) and
+    every array of `payloads` (parallel to keys) becomes a derived int64
+    column of the scan, NULL where the row has no match (a left join);
+    inner=True drops those rows. keys and payloads are sequences / ndarrays
+    of ints (copied at scan begin) or contiguous int64 torch tensors on the
+    GPU, all of them, which are then read in place at every stage() and kept
+    alive by the scan."""
+
+    def __init__(self, key_col, keys, payloads, inner=False):
+        self.key_col = key_col
+        self.keys = keys
+        self.payloads = list(payloads)
+        self.inner = bool(inner)
+
+
+def _is_torch(v):
+    return type(v).__module__.split(".")[0] == "torch"
+
+
+def make_lookups(lookups):
+    """(LookupIn array or None, n) for cstripe_scan_begin_lookups; the array
+    keeps every buffer it points at alive"""
+    import numpy as np
+    if not lookups:
+        return None, 0
+    arr = (LookupIn * len(lookups))()
+    keep = []
+    for i, lk in enumerate(lookups):
+        arrays = [lk.keys] + lk.payloads
+        dev = [_is_torch(a) for a in arrays]
+        if any(dev) and not all(dev):
+            raise CStripeError(f"lookup {i}: keys and payloads must all be host arrays "
+                               "or all GPU tensors")
+        arr[i].key_column = lk.key_col
+        arr[i].n_payloads = len(lk.payloads)
+        arr[i].flags = LOOKUP_INNER if lk.inner else 0
+        n = len(lk.keys)
+        arr[i].n = n
+        ptrs = []
+        if all(dev):
+            import torch
+            for a in arrays:
+                if not a.is_cuda or str(a.dtype) != "torch.int64" or not a.is_contiguous() \
+                        or a.dim() != 1 or a.numel() != n:
+                    raise CStripeError(f"lookup {i}: a device map needs contiguous 1-d int64 "
+                                       "GPU tensors of one length")
+                ptrs.append(a.data_ptr() if n else None)
+                keep.append(a)
+            torch.cuda.synchronize(arrays[0].device)
+            arr[i].on_device = 1
+        else:
+            for a in arrays:
+                if len(a) != n:
+                    raise CStripeError(f"lookup {i}: keys and payloads differ in length")
+                h = np.ascontiguousarray(np.asarray(a).astype(np.int64, copy=False)
+                                         if n else np.zeros(0, np.int64))
+                ptrs.append(h.ctypes.data_as(C.c_void_p).value if n else None)
+                keep.append(h)
+        arr[i].keys = ptrs[0]
+        for p_, q in enumerate(ptrs[1:MAX_LOOKUP_PAYLOADS + 1]):
+            arr[i].payloads[p_] = q
+    arr._keep = keep
+    return arr, len(lookups)
+
+
 class AggSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("col_a", C.c_int32), ("col_b", C.c_int32),
                 ("col_c", C.c_int32), ("one", C.c_int64)]
@@ -210,6 +291,16 @@ _scan_begin_sets = _sig("cstripe_scan_begin_sets", C.c_void_p,
                         [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32,
                          C.POINTER(TextConst), C.c_uint32,
                          C.POINTER(ValueSet), C.c_uint32])
+_scan_begin_lookups = _sig("cstripe_scan_begin_lookups", C.c_void_p,
+                           [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32,
+                            C.POINTER(TextConst), C.c_uint32,
+                            C.POINTER(ValueSet), C.c_uint32,
+                            C.POINTER(LookupIn), C.c_uint32])
+_scan_column_count = _sig("cstripe_scan_column_count", C.c_uint32, [C.c_void_p])
+_last_lookup_ms = _sig("cstripe_scan_last_lookup_ms", C.c_int,
+                       [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)])
+_lookup_form = _sig("cstripe_scan_lookup_form", C.c_int,
+                    [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)])
 _last_set_ms = _sig("cstripe_scan_last_set_ms", C.c_int,
                     [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)])
 _set_form = _sig("cstripe_scan_set_form", C.c_int,
@@ -542,8 +633,10 @@ class Reader:
         _check(_column_def(self._h, i, C.byref(d)), "column_def")
         return d.name.decode(), d.type, d.scale
 
-    def scan(self, cols_mask=0, preds=()):
-        return Scan(self, cols_mask, preds)
+    def scan(self, cols_mask=0, preds=(), lookups=()):
+        """lookups: a list of Lookup — each payload becomes a derived int64
+        column with id column_count + ..., see Scan.derived()"""
+        return Scan(self, cols_mask, preds, lookups)
 
 
 def make_preds(preds):
@@ -842,9 +935,17 @@ def merge_topn(results, order, limit, offset=0, text=False):
 
 
 class Scan:
-    def __init__(self, reader, cols_mask, preds):
+    def __init__(self, reader, cols_mask, preds, lookups=()):
         self._sets = None
-        if any(_is_set_pred(p) for p in preds):   # IN / NOT IN: value sets
+        self._lookups = None
+        self._lookup_payloads = [len(lk.payloads) for lk in lookups]
+        if lookups:                               # N:1 joins: derived columns
+            self._preds, self._texts, n_texts, self._sets, n_sets = make_preds_sets(preds)
+            self._lookups, n_lk = make_lookups(list(lookups))
+            self._h = _scan_begin_lookups(reader._h, cols_mask, self._preds, len(preds),
+                                          self._texts, n_texts, self._sets, n_sets,
+                                          self._lookups, n_lk)
+        elif any(_is_set_pred(p) for p in preds):   # IN / NOT IN: value sets
             self._preds, self._texts, n_texts, self._sets, n_sets = make_preds_sets(preds)
             self._h = _scan_begin_sets(reader._h, cols_mask, self._preds, len(preds),
                                        self._texts, n_texts, self._sets, n_sets)
@@ -860,11 +961,18 @@ class Scan:
         self.reader = reader
         self._reader = reader
         # pred columns are implicitly projected (scan_begin does the same)
-        self._mask = cols_mask
+        ntab = reader.column_count
+        self._mask = cols_mask & ((1 << ntab) - 1)
         for p in preds:
-            self._mask |= 1 << p[0]
+            if p[0] < ntab:
+                self._mask |= 1 << p[0]
+        for lk in lookups:
+            self._mask |= 1 << lk.key_col        # key columns are read too
         if self._mask == 0:
             self._mask = 1
+        # derived columns are always projected
+        for c in range(ntab, ntab + sum(self._lookup_payloads)):
+            self._mask |= 1 << c
         self._device = -1
 
     def end(self):
@@ -952,6 +1060,41 @@ class Scan:
             raise CStripeError(f"scan_set_form failed (rc={rc}): {errmsg()}")
         return rc, size.value
 
+    def column_count(self):
+        """table columns + derived (lookup payload) columns of this scan
+        (cstripe_scan_column_count). A method, as the C entry is a call on
+        the scan — unlike the Reader.column_count property, which it equals
+        for a scan without lookups."""
+        return _scan_column_count(self._h)
+
+    def derived(self, l, p):
+        """column id of payload p of lookup l"""
+        if not (0 <= l < len(self._lookup_payloads) and 0 <= p < self._lookup_payloads[l]):
+            raise CStripeError(f"derived: no payload {p} of lookup {l} in this scan")
+        return self._reader.column_count + sum(self._lookup_payloads[:l]) + p
+
+    def last_lookup_ms(self):
+        """(build, probe) device ms of the last stage()'s lookup work, all
+        lookups together; zeros without one"""
+        b, p = C.c_double(), C.c_double()
+        _check(_last_lookup_ms(self._h, C.byref(b), C.byref(p)), "scan_last_lookup_ms")
+        return b.value, p.value
+
+    def lookup_form(self, i):
+        """(form, size) of lookup i's table at the last stage(): form is
+        LOOKUP_FORM_NONE (unstaged), LOOKUP_FORM_HASH or LOOKUP_FORM_DIRECT,
+        size its slots or entries"""
+        size = C.c_uint64()
+        rc = _lookup_form(self._h, i, C.byref(size))
+        if rc < 0:
+            raise CStripeError(f"scan_lookup_form failed (rc={rc}): {errmsg()}")
+        return rc, size.value
+
+    def _col_type(self, c):
+        """cstripe type of a table or derived (I64) column id"""
+        ntab = self._reader.column_count
+        return I64 if c >= ntab else self._reader.column_def(c)[1]
+
     def _decode_ranks(self, col, ranks, nulls):
         """object array of bytes / None from a VARTEXT column's ranks"""
         import numpy as np
@@ -1000,7 +1143,7 @@ class Scan:
             res["text_keys"] = {
                 k: self._decode_ranks(c, res["keys"][k], res["key_nulls"][k])
                 for k, c in enumerate(key_cols)
-                if self._reader.column_def(c)[1] == VARTEXT}
+                if self._col_type(c) == VARTEXT}
         return res
 
     @property
@@ -1062,7 +1205,7 @@ class Scan:
         """caller-owned destinations of `cap` rows for select / select_topn:
         (values, nulls, row_numbers, Rows) — numpy arrays, or torch tensors
         on the scan's device"""
-        ncols = self._reader.column_count
+        ncols = self.column_count()
         if device:
             import torch
             dev = torch.device("cuda", self._device if self._device >= 0
@@ -1135,15 +1278,14 @@ class Scan:
         A VARTEXT column comes back as int32 dictionary ranks (text_dict);
         decode_text=True (host mode, needs want_nulls) adds "text":
         {col: object array of bytes / None}."""
-        r = self._reader
-        ncols = r.column_count
+        ncols = self.column_count()
         if cols is None:
             cols = [c for c in range(ncols) if (self._mask >> c) & 1]
         cols = list(cols)
         for c in cols:
             if not 0 <= c < ncols:
                 raise CStripeError(f"select: column {c} out of range")
-        types = {c: r.column_def(c)[1] for c in cols}
+        types = {c: self._col_type(c) for c in cols}
         n = self.select_count()
         m_ms, o_ms, _ = self.last_select_ms
         d_ms = self.last_decode_ms
@@ -1192,8 +1334,7 @@ class Scan:
         (device ms per stage) and "text_cols" (the VARTEXT columns among
         "values", whose int32 ranks are per scan). cols, want_nulls,
         want_row_numbers, device and decode_text as in select()."""
-        r = self._reader
-        ncols = r.column_count
+        ncols = self.column_count()
         keys = parse_order(order)
         if cols is None:
             cols = [c for c in range(ncols) if (self._mask >> c) & 1]
@@ -1201,7 +1342,7 @@ class Scan:
         for c in cols:
             if not 0 <= c < ncols:
                 raise CStripeError(f"select_topn: column {c} out of range")
-        types = {c: r.column_def(c)[1] for c in cols}
+        types = {c: self._col_type(c) for c in cols}
         # every destination holds `limit` entries; an out-of-range limit is
         # the library's error, so only the allocation is clamped
         cap = min(max(int(limit), 1), MAX_TOPN)

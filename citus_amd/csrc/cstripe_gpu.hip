@@ -212,7 +212,12 @@ struct cs_gpu_state {
     struct MemberSlot { uint32_t col, set, proj; };
     std::vector<MemberSlot> mslots;
     std::vector<int> mpred_slot;
-    std::vector<void *> set_bufs;    /* set tables (sets_build) */
+    std::vector<void *> set_bufs;    /* set and lookup tables (sets_build,
+                                      * lookups_build) */
+    /* lookups: one derived slot (a projected sparse I64 column in scratch,
+     * after the member slots) per payload; proj_of_col covers their ids */
+    struct DerivedSlot { uint32_t lookup, payload, proj; };
+    std::vector<DerivedSlot> dslots;
 };
 
 /* ---------------- error helper ---------------- */
@@ -3250,6 +3255,7 @@ void csgpu_release(cstripe_scan *s)
     delete g;
     s->gpu = nullptr;
     for (cs_value_set &vs : s->sets) { vs.form = 0; vs.form_size = 0; }
+    for (cs_lookup &lk : s->lookups) { lk.form = 0; lk.form_size = 0; }
 }
 
 uint64_t csgpu_staged_bytes(const cstripe_scan *s)
@@ -3286,6 +3292,7 @@ struct VtTemps {
 };
 static int vartext_build(cstripe_scan *s, VtTemps &vt);
 static int sets_build(cstripe_scan *s, VtTemps &st);
+static int lookups_build(cstripe_scan *s, VtTemps &lt);
 
 int csgpu_stage(cstripe_scan *s, int device_id)
 {
@@ -3339,6 +3346,22 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         g->mpred_slot[i] = found;
     }
     if (!g->mslots.empty()) g->fusable = false;
+    /* derived slots of the lookups' payload columns, after the member slots */
+    for (size_t l = 0; l < s->lookups.size(); l++)
+        for (uint32_t pl = 0; pl < s->lookups[l].n_payloads; pl++) {
+            if (n_proj >= MAX_PROJ) {
+                cs_set_err("gpu_stage: %u projected columns plus the derived columns of the "
+                           "lookups exceed the %d slots of one scan (lookup %u)",
+                           n_proj, MAX_PROJ, (unsigned)l);
+                csgpu_release(s);
+                return CSTRIPE_ERR_ARG;
+            }
+            g->dslots.push_back({(uint32_t)l, pl, n_proj});
+            g->proj_of_col[s->lookups[l].first_col + pl] = (int)n_proj;
+            g->proj_type[n_proj] = CSTRIPE_I64;
+            n_proj++;
+        }
+    if (!g->dslots.empty()) { g->fusable = false; g->all_dense = false; }
     g->n_proj = n_proj;
     g->n_groups = (uint32_t)s->sel.size();
 
@@ -3397,9 +3420,20 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         for (const auto &ms : g->mslots)
             scratch_bytes = align_up(scratch_bytes, 16) +
                             align_up((uint64_t)st.nodes[ms.col][sc.chunk].n.n_present, 16);
+        /* derived columns: per lookup one device-written exists bitmap and
+         * rank table (the payloads share them), per payload room for one
+         * value per non-NULL key, in a scratch region no decode segment
+         * writes */
+        for (const auto &lk : s->lookups) {
+            data_bytes = align_up(data_bytes, 8) + align_up((rows + 7) / 8, 8);
+            rank_words += (rows + 63) / 64;
+            for (uint32_t pl = 0; pl < lk.n_payloads; pl++)
+                scratch_bytes = align_up(scratch_bytes, 16) +
+                                align_up((uint64_t)st.nodes[lk.key_column][sc.chunk].n.n_present * 8, 16);
+        }
     }
     (void)zstd_host;
-    if (any_vartext || !g->mslots.empty())
+    if (any_vartext || !g->mslots.empty() || !g->dslots.empty())
         scratch_bytes += 64;        /* the R-row windowed loads of the dense
                                      * kernels reach up to R-1 entries past a
                                      * rank array's end */
@@ -3673,6 +3707,27 @@ int csgpu_stage(cstripe_scan *s, int device_id)
             spos += align_up((uint64_t)st.nodes[ms.col][sc.chunk].n.n_present, 16);
             h_colloc[(uint64_t)gi * n_proj + ms.proj] = cl;
         }
+        for (size_t l = 0, ds = 0; l < s->lookups.size(); l++) {
+            /* a derived column reads as a sparse I64 column in scratch; its
+             * bitmap (zero here), rank words and values are written on the
+             * device (lookups_build) */
+            const cs_lookup &lk = s->lookups[l];
+            ColLoc cl{};
+            cl.type = CSTRIPE_I64;
+            cl.width = 8;
+            cl.flags = 1;
+            dpos = align_up(dpos, 8);
+            cl.exists_off = dpos;
+            dpos += align_up((rows + 7) / 8, 8);
+            cl.rank_off = (uint32_t)h_rank.size();
+            h_rank.resize(h_rank.size() + (rows + 63) / 64, 0);
+            for (uint32_t pl = 0; pl < lk.n_payloads; pl++, ds++) {
+                spos = align_up(spos, 16);
+                cl.val_off = spos;
+                spos += align_up((uint64_t)st.nodes[lk.key_column][sc.chunk].n.n_present * 8, 16);
+                h_colloc[(uint64_t)gi * n_proj + g->dslots[ds].proj] = cl;
+            }
+        }
     }
 
     /* invariant: the layout pass and the fill pass must agree exactly —
@@ -3773,6 +3828,17 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         VtTemps st;
         int rc = sets_build(s, st);
         st.release();
+        if (rc != CSTRIPE_OK) {
+            csgpu_release(s);
+            s->text_dicts.clear();
+            return rc;
+        }
+    }
+    s->last_lookup_build_ms = s->last_lookup_probe_ms = 0;
+    if (!g->dslots.empty()) {
+        VtTemps lt;
+        int rc = lookups_build(s, lt);
+        lt.release();
         if (rc != CSTRIPE_OK) {
             csgpu_release(s);
             s->text_dicts.clear();
@@ -4381,7 +4447,7 @@ static int vartext_build(cstripe_scan *s, VtTemps &vt)
     /* ---- VARTEXT predicates -> integer atoms over ranks (cstripe.h) ---- */
     for (size_t i = 0; i < s->preds.size(); i++) {
         const cstripe_pred &q = s->preds[i];
-        if (r->cols[q.column].type != CSTRIPE_VARTEXT) continue;
+        if (cs_col_type(s, q.column) != CSTRIPE_VARTEXT) continue;
         if (g->mpred_slot[i] >= 0) continue;   /* IN / NOT IN: sets_build */
         const cs_text_dict &d = s->text_dicts[q.column];
         const std::string &cst = s->text_consts[(size_t)q.ival];
@@ -4755,6 +4821,393 @@ static int sets_build(cstripe_scan *s, VtTemps &st)
     return CSTRIPE_OK;
 }
 
+/* =====================================================================
+ * Lookups — the device N:1 join with payload columns.
+ *
+ * No query kernel knows about lookups. At stage each payload of each lookup
+ * becomes a DERIVED column: a sparse I64 column in scratch whose exists
+ * bitmap, rank table and compacted values are all written here, so every
+ * surface reads it through col_value like a table column with NULLs.
+ *   build   lookup_build_kernel: key -> entry index, one table per lookup
+ *           (its payloads share one probe). Direct form: a u32 entry array
+ *           over [lo, hi] claimed by 32-bit atomicCAS. Hash form: the
+ *           open-addressing table of the value sets (64-bit atomicCAS claims,
+ *           set_slot, linear probing; key -1 is the EMPTY pattern and lives
+ *           in a flag + entry word) plus a u32 entry word per slot, stored by
+ *           the claim's winner. An insert that meets its own key already
+ *           claimed raises the duplicate flag.
+ *   probe   lookup_probe_kernel: one wave per 64-row word reads the key
+ *           through col_value (NULL key: no match), looks it up with plain
+ *           loads (the table is read-only by then), ballots the exists word
+ *           and stores each row's entry index into a temporary u32 array
+ *   rank    lookup_rank_kernel: one block per chunk group scans the words'
+ *           popcounts into the rank table (present values before word w)
+ *   gather  lookup_gather_kernel: each matched row stores payload[p][entry]
+ *           at rank[w] + popc(below) for every payload
+ * Wave width is 64 throughout; the ballot of a partial last word has its
+ * unused high bits zero because lanes past the group's rows never match.
+ * ===================================================================== */
+
+#define LK_NONE 0xFFFFFFFFu
+#define LK_WAVES (AGG_BLOCK / WAVE)
+#define LK_BATCH_ROWS (1ull << 26)      /* rows per probe / gather batch */
+
+struct LkTable {
+    const unsigned long long *keys;   /* hash form: key words */
+    const uint32_t *ents;             /* hash form: entry index per slot */
+    const uint32_t *neg1;             /* hash form: [0] key -1 present, [1] its entry */
+    const uint32_t *direct;           /* direct form, else null */
+    int64_t lo, hi;                   /* direct range */
+    uint64_t mask;                    /* hash: slots - 1 */
+    uint32_t shift;                   /* hash: 64 - log2(slots) */
+    uint32_t pad;
+};
+
+struct LkPayloads {
+    const int64_t *src[CSTRIPE_MAX_LOOKUP_PAYLOADS];
+    uint32_t proj[CSTRIPE_MAX_LOOKUP_PAYLOADS];
+    uint32_t n;
+    uint32_t pad;
+};
+
+/* insert keys[0..n) -> entry index. flag bit 0: a duplicate build key; bit 1:
+ * a key outside the direct range (a device array that changed since begin;
+ * the index never leaves the allocation). Hash: slots >= 2n, so a probe
+ * sequence always meets its key or an EMPTY slot. */
+__global__ __launch_bounds__(AGG_BLOCK) void lookup_build_kernel(
+    const int64_t *__restrict__ keys, uint64_t n, unsigned long long *hkeys,
+    uint32_t *hents, uint32_t *neg1, uint32_t *direct, uint32_t *flag, LkTable t)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const int64_t v = keys[i];
+        if (direct) {
+            if (v < t.lo || v > t.hi) { atomicOr(flag, 2u); continue; }
+            const uint64_t d = (uint64_t)v - (uint64_t)t.lo;
+            if (atomicCAS(&direct[d], LK_NONE, (uint32_t)i) != LK_NONE) atomicOr(flag, 1u);
+            continue;
+        }
+        const unsigned long long key = (unsigned long long)v;
+        if (key == SET_EMPTY) {
+            if (atomicCAS(&neg1[0], 0u, 1u) == 0u) neg1[1] = (uint32_t)i;
+            else atomicOr(flag, 1u);
+            continue;
+        }
+        uint64_t h = set_slot(key, t.shift);
+        for (uint64_t tries = 0; tries <= t.mask; tries++) {
+            const unsigned long long prev = atomicCAS(&hkeys[h], SET_EMPTY, key);
+            if (prev == SET_EMPTY) { hents[h] = (uint32_t)i; break; }
+            if (prev == key) { atomicOr(flag, 1u); break; }
+            h = (h + 1) & t.mask;
+        }
+    }
+}
+
+__device__ inline uint32_t lookup_find(const LkTable &t, int64_t v)
+{
+    if (t.direct) {
+        if (v < t.lo || v > t.hi) return LK_NONE;
+        return t.direct[(uint64_t)v - (uint64_t)t.lo];
+    }
+    const unsigned long long key = (unsigned long long)v;
+    if (key == SET_EMPTY) return t.neg1[0] ? t.neg1[1] : LK_NONE;
+    uint64_t h = set_slot(key, t.shift);
+    for (uint64_t tries = 0; tries <= t.mask; tries++) {
+        const unsigned long long k = t.keys[h];
+        if (k == key) return t.ents[h];
+        if (k == SET_EMPTY) return LK_NONE;
+        h = (h + 1) & t.mask;
+    }
+    return LK_NONE;
+}
+
+/* blocks_pg blocks per chunk group of the batch [g0, g0 + gridDim.x /
+ * blocks_pg), one wave per 64-row word; ents holds the batch's rows, the
+ * first of which is table-wide row ent_base. The exists
+ * region of a derived column is (rows + 63) / 64 whole words (8-byte padded
+ * at layout), so the word store stays inside it. */
+__global__ __launch_bounds__(AGG_BLOCK) void lookup_probe_kernel(
+    const uint8_t *data, const uint8_t *__restrict__ scratch,
+    const uint32_t *__restrict__ rank, uint8_t *data_w,
+    const GroupDesc *__restrict__ groups, const ColLoc *__restrict__ colloc,
+    const uint64_t *__restrict__ rowbase, uint32_t *__restrict__ ents,
+    uint32_t n_proj, uint32_t key_proj, uint32_t d_proj, uint32_t blocks_pg,
+    uint32_t g0, uint64_t ent_base, LkTable t)
+{
+    const uint32_t gi = g0 + blockIdx.x / blocks_pg;
+    const uint32_t w = (blockIdx.x % blocks_pg) * LK_WAVES + threadIdx.x / WAVE;
+    const uint32_t rows = groups[gi].row_count;
+    if ((uint64_t)w * WAVE >= rows) return;            /* wave-uniform */
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint32_t row = w * WAVE + lane;
+    uint32_t e = LK_NONE;
+    if (row < rows) {
+        const ColLoc key = colloc[(uint64_t)gi * n_proj + key_proj];
+        int64_t iv = 0;
+        double fv = 0;
+        if (col_value(data, scratch, rank, key, row, iv, fv)) e = lookup_find(t, iv);
+        ents[rowbase[gi] - ent_base + row] = e;
+    }
+    const uint64_t word = __ballot(e != LK_NONE);
+    if (lane == 0)
+        ((uint64_t *)(data_w + colloc[(uint64_t)gi * n_proj + d_proj].exists_off))[w] = word;
+}
+
+/* one block per chunk group: exclusive scan of the bitmap words' popcounts */
+__global__ __launch_bounds__(AGG_BLOCK) void lookup_rank_kernel(
+    const uint8_t *__restrict__ data, uint32_t *rank,
+    const GroupDesc *__restrict__ groups, const ColLoc *__restrict__ colloc,
+    uint32_t n_proj, uint32_t d_proj, uint32_t g0)
+{
+    __shared__ uint32_t wsum[LK_WAVES];
+    const uint32_t gi = g0 + blockIdx.x;
+    const uint32_t words = (groups[gi].row_count + 63) / 64;
+    const ColLoc cl = colloc[(uint64_t)gi * n_proj + d_proj];
+    const uint64_t *bm = (const uint64_t *)(data + cl.exists_off);
+    const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    uint32_t base = 0;
+    for (uint32_t w0 = 0; w0 < words; w0 += AGG_BLOCK) {
+        const uint32_t w = w0 + threadIdx.x;
+        const uint32_t c = w < words ? (uint32_t)__popcll(bm[w]) : 0u;
+        uint32_t incl = c;
+        for (uint32_t off = 1; off < WAVE; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off, WAVE);
+            if (lane >= off) incl += up;
+        }
+        if (lane == WAVE - 1) wsum[wave] = incl;
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        for (uint32_t k = 0; k < LK_WAVES; k++) {
+            if (k < wave) pre += wsum[k];
+            tot += wsum[k];
+        }
+        if (w < words) rank[cl.rank_off + w] = base + pre + incl - c;
+        base += tot;
+        __syncthreads();
+    }
+}
+
+/* the probe's geometry; a matched row's value index is below the key's
+ * n_present, which sized the value region */
+__global__ __launch_bounds__(AGG_BLOCK) void lookup_gather_kernel(
+    const uint8_t *__restrict__ data, uint8_t *scratch,
+    const uint32_t *__restrict__ rank, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, const uint64_t *__restrict__ rowbase,
+    const uint32_t *__restrict__ ents, uint32_t n_proj, uint32_t blocks_pg,
+    uint32_t g0, uint64_t ent_base, LkPayloads pp)
+{
+    const uint32_t gi = g0 + blockIdx.x / blocks_pg;
+    const uint32_t w = (blockIdx.x % blocks_pg) * LK_WAVES + threadIdx.x / WAVE;
+    const uint32_t rows = groups[gi].row_count;
+    if ((uint64_t)w * WAVE >= rows) return;
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint32_t row = w * WAVE + lane;
+    const ColLoc *cls = colloc + (uint64_t)gi * n_proj;
+    const uint64_t word = ((const uint64_t *)(data + cls[pp.proj[0]].exists_off))[w];
+    const uint64_t bit = 1ull << lane;
+    if (!(word & bit)) return;
+    const uint32_t idx = rank[cls[pp.proj[0]].rank_off + w] + (uint32_t)__popcll(word & (bit - 1));
+    const uint32_t e = ents[rowbase[gi] - ent_base + row];
+    #pragma unroll
+    for (uint32_t p = 0; p < CSTRIPE_MAX_LOOKUP_PAYLOADS; p++)
+        if (p < pp.n)
+            ((int64_t *)(scratch + cls[pp.proj[p]].val_off))[idx] = pp.src[p][e];
+}
+
+/* temporaries of lookups_build: rowbase, entry indexes and the flag, plus
+ * the uploaded keys and payloads of every host map */
+static_assert(3 + CSTRIPE_MAX_LOOKUPS * (1 + CSTRIPE_MAX_LOOKUP_PAYLOADS) <=
+                  sizeof(VtTemps::bufs) / sizeof(void *),
+              "VtTemps::bufs is too small for the lookups' temporaries");
+
+static int lookups_build(cstripe_scan *s, VtTemps &lt)
+{
+    cs_gpu_state *g = s->gpu;
+    const uint32_t n_proj = g->n_proj;
+    int force = 0;                         /* CSTRIPE_LOOKUP_FORM_*, 0 = choose */
+    if (const char *e = getenv("CSTRIPE_LOOKUP_FORM")) {
+        if (!strcmp(e, "hash")) force = CSTRIPE_LOOKUP_FORM_HASH;
+        else if (!strcmp(e, "direct")) force = CSTRIPE_LOOKUP_FORM_DIRECT;
+    }
+    for (hipEvent_t &e : lt.ev) HIP_TRY(hipEventCreate(&e));
+
+    /* the key columns must be readable: decode what lands in scratch (as
+     * sets_build does; the derived regions survive later decodes for the
+     * same reason the membership regions do) */
+    bool need_decode = false;
+    for (const cs_lookup &lk : s->lookups)
+        if (g->col_scratch[(size_t)g->proj_of_col[lk.key_column]]) need_decode = true;
+    if (need_decode && g->n_groups) {
+        HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+        { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+        int h_err = 0;
+        HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    }
+
+    const uint32_t words_pg = (g->max_group_rows + 63) / 64;
+    const uint32_t blocks_pg = words_pg ? (words_pg + LK_WAVES - 1) / LK_WAVES : 1;
+    if ((uint64_t)g->n_groups * blocks_pg >= (1ull << 31)) { cs_set_err("gpu_stage: too many words for the lookup probe"); return CSTRIPE_ERR_ARG; }
+
+    /* per-row entry indexes of one lookup and one batch of chunk groups at a
+     * time: probe, rank scan and gather run batch by batch, so the temporary
+     * stays at 4 B x LK_BATCH_ROWS (256 MB) however large the scan is.
+     * CSTRIPE_LOOKUP_BATCH_ROWS (environment, read per stage) overrides the
+     * batch size; a batch always holds at least one chunk group. */
+    uint64_t batch_rows = LK_BATCH_ROWS;
+    if (const char *e = getenv("CSTRIPE_LOOKUP_BATCH_ROWS")) {
+        const long long v = atoll(e);
+        if (v > 0) batch_rows = (uint64_t)v;
+    }
+    struct Batch { uint32_t g0, ng; uint64_t first_row; };
+    std::vector<Batch> batches;
+    std::vector<uint64_t> h_rowbase(g->n_groups);
+    uint64_t total_rows = 0, max_batch = 0;
+    for (uint32_t gi = 0; gi < g->n_groups; gi++) {
+        const cs_selchunk &sc = s->sel[gi];
+        const uint64_t rows = s->r->stripes[sc.stripe].group_rows[sc.chunk];
+        h_rowbase[gi] = total_rows;
+        if (batches.empty() ||
+            total_rows + rows - batches.back().first_row > batch_rows)
+            batches.push_back({gi, 0, total_rows});
+        batches.back().ng++;
+        total_rows += rows;
+        max_batch = std::max(max_batch, total_rows - batches.back().first_row);
+    }
+    uint64_t *d_rowbase = nullptr;
+    uint32_t *d_ents = nullptr, *d_flag = nullptr;
+    HIP_TRY(lt.alloc(d_rowbase, (uint64_t)g->n_groups * sizeof(uint64_t)));
+    HIP_TRY(lt.alloc(d_ents, max_batch * sizeof(uint32_t)));
+    HIP_TRY(lt.alloc(d_flag, sizeof(uint32_t)));
+    if (g->n_groups)
+        HIP_TRY(hipMemcpyAsync(d_rowbase, h_rowbase.data(), h_rowbase.size() * sizeof(uint64_t),
+                               hipMemcpyHostToDevice, g->stream));
+    float ms_f = 0;
+
+    for (size_t l = 0; l < s->lookups.size(); l++) {
+        cs_lookup &lk = s->lookups[l];
+        const uint64_t n = lk.n;
+        if (lk.on_device && lk.dev_id != g->device) {
+            cs_set_err("gpu_stage: lookup %u lives on device %d, the scan is staged on device %d",
+                       (unsigned)l, lk.dev_id, g->device);
+            return CSTRIPE_ERR_ARG;
+        }
+        const int64_t lo = n ? lk.klo : 0, hi = n ? lk.khi : 0;
+        /* ---- form ---- */
+        const uint64_t span = (uint64_t)hi - (uint64_t)lo;             /* hi - lo, exact */
+        const bool direct_legal = span < 0xFFFFFFFFull;                /* range < 2^32 */
+        const uint64_t want = std::max<uint64_t>(1ull << 16, 4 * n);
+        int form = (direct_legal && span + 1 <= want) ? CSTRIPE_LOOKUP_FORM_DIRECT
+                                                      : CSTRIPE_LOOKUP_FORM_HASH;
+        if (force == CSTRIPE_LOOKUP_FORM_HASH) form = force;
+        if (force == CSTRIPE_LOOKUP_FORM_DIRECT && direct_legal) form = force;
+        /* ---- the build side on the device ---- */
+        const int64_t *d_keys = lk.dev_keys;
+        LkPayloads pp{};
+        pp.n = lk.n_payloads;
+        for (size_t ds = 0; ds < g->dslots.size(); ds++)
+            if (g->dslots[ds].lookup == l) pp.proj[g->dslots[ds].payload] = g->dslots[ds].proj;
+        for (uint32_t p = 0; p < lk.n_payloads; p++) pp.src[p] = lk.dev_payloads[p];
+        if (!lk.on_device && n) {
+            int64_t *up = nullptr;
+            HIP_TRY(lt.alloc(up, n * sizeof(int64_t)));
+            HIP_TRY(hipMemcpyAsync(up, lk.keys.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+            d_keys = up;
+            for (uint32_t p = 0; p < lk.n_payloads; p++) {
+                HIP_TRY(lt.alloc(up, n * sizeof(int64_t)));
+                HIP_TRY(hipMemcpyAsync(up, lk.payloads[p].data(), n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+                pp.src[p] = up;
+            }
+        }
+        /* ---- table: build time = clearing it + the insert kernel ---- */
+        unsigned long long *d_hkeys = nullptr;
+        uint32_t *d_hents = nullptr, *d_neg1 = nullptr, *d_direct = nullptr;
+        LkTable t{};
+        t.lo = lo;
+        t.hi = hi;
+        uint64_t size;
+        HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), g->stream));
+        HIP_TRY(hipEventRecord(lt.ev[0], g->stream));
+        if (form == CSTRIPE_LOOKUP_FORM_DIRECT) {
+            size = span + 1;
+            void *q = nullptr;
+            HIP_TRY(hipMalloc(&q, size * 4));
+            g->set_bufs.push_back(q);
+            d_direct = (uint32_t *)q;
+            HIP_TRY(hipMemsetAsync(d_direct, 0xFF, size * 4, g->stream));
+        } else {
+            uint64_t slots = 2;
+            uint32_t lg = 1;
+            while (slots < 2 * n) { slots <<= 1; lg++; }
+            size = slots;
+            void *q = nullptr;
+            HIP_TRY(hipMalloc(&q, slots * 12 + 8));
+            g->set_bufs.push_back(q);
+            d_hkeys = (unsigned long long *)q;
+            d_hents = (uint32_t *)(d_hkeys + slots);
+            d_neg1 = d_hents + slots;
+            HIP_TRY(hipMemsetAsync(d_hkeys, 0xFF, slots * 8, g->stream));
+            HIP_TRY(hipMemsetAsync(d_neg1, 0, 8, g->stream));
+            t.mask = slots - 1;
+            t.shift = 64 - lg;
+        }
+        if (n) {
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((n + AGG_BLOCK - 1) / AGG_BLOCK, 4096);
+            hipLaunchKernelGGL(lookup_build_kernel, dim3(grid), dim3(AGG_BLOCK), 0, g->stream,
+                               d_keys, n, d_hkeys, d_hents, d_neg1, d_direct, d_flag, t);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(lt.ev[1], g->stream));
+        uint32_t h_flag = 0;
+        HIP_TRY(hipMemcpyAsync(&h_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        (void)hipEventElapsedTime(&ms_f, lt.ev[0], lt.ev[1]);
+        s->last_lookup_build_ms += ms_f;
+        if (h_flag & 1u) {
+            cs_set_err("gpu_stage: lookup %u: duplicate build keys in the device map "
+                       "(build keys must be distinct)", (unsigned)l);
+            return CSTRIPE_ERR_ARG;
+        }
+        if (h_flag & 2u) {
+            cs_set_err("gpu_stage: lookup %u: a device build key lies outside the range found "
+                       "at scan begin (the key array changed)", (unsigned)l);
+            return CSTRIPE_ERR_ARG;
+        }
+        t.keys = d_hkeys;
+        t.ents = d_hents;
+        t.neg1 = d_neg1;
+        t.direct = d_direct;
+        lk.form = form;
+        lk.form_size = size;
+        /* ---- probe, rank scan, gather ---- */
+        if (g->n_groups == 0) continue;
+        HIP_TRY(hipEventRecord(lt.ev[2], g->stream));
+        for (const Batch &b : batches) {
+            /* one stream: a batch's gather is done with d_ents before the
+             * next batch's probe overwrites it */
+            const uint32_t grid = b.ng * blocks_pg;
+            hipLaunchKernelGGL(lookup_probe_kernel, dim3(grid), dim3(AGG_BLOCK), 0, g->stream,
+                               g->d_data, g->d_scratch, g->d_rank, g->d_data, g->d_groups, g->d_colloc,
+                               d_rowbase, d_ents, n_proj, (uint32_t)g->proj_of_col[lk.key_column],
+                               pp.proj[0], blocks_pg, b.g0, b.first_row, t);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(lookup_rank_kernel, dim3(b.ng), dim3(AGG_BLOCK), 0, g->stream,
+                               g->d_data, g->d_rank, g->d_groups, g->d_colloc, n_proj, pp.proj[0], b.g0);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(lookup_gather_kernel, dim3(grid), dim3(AGG_BLOCK), 0, g->stream,
+                               g->d_data, g->d_scratch, g->d_rank, g->d_groups, g->d_colloc,
+                               d_rowbase, d_ents, n_proj, blocks_pg, b.g0, b.first_row, pp);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(lt.ev[3], g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        (void)hipEventElapsedTime(&ms_f, lt.ev[2], lt.ev[3]);
+        s->last_lookup_probe_ms += ms_f;
+    }
+    return CSTRIPE_OK;
+}
+
 /* true when the spec reads a VARTEXT column as a value: its ranks are a
  * per-scan coding, so only COUNT_COL (presence) means anything */
 static bool agg_reads_vartext(const cstripe_reader *r, const cstripe_agg_spec &a)
@@ -4779,13 +5232,12 @@ static bool agg_reads_vartext(const cstripe_reader *r, const cstripe_agg_spec &a
 static void fill_preds(const cstripe_scan *s, AggParams &p)
 {
     const cs_gpu_state *g = s->gpu;
-    const cstripe_reader *r = s->r;
     p.n_preds = (uint32_t)s->preds.size();
     for (uint32_t i = 0; i < p.n_preds; i++) {
         const cstripe_pred &q = s->preds[i];
         p.preds[i].proj = (uint16_t)g->proj_of_col[q.column];
         p.preds[i].op = (uint8_t)q.op;
-        uint8_t t = r->cols[q.column].type;
+        uint8_t t = cs_col_type(s, q.column);
         p.preds[i].is_float = (t == CSTRIPE_F32 || t == CSTRIPE_F64) ? 1 : 0;
         p.preds[i].gend = (i + 1 == p.n_preds ||
                            s->preds[i + 1].or_group != q.or_group) ? 1 : 0;
@@ -4807,10 +5259,12 @@ static void fill_preds(const cstripe_scan *s, AggParams &p)
     }
 }
 
-/* projected slot of a table column, -1 when out of range or not projected */
+/* projected slot of a table or derived column id — with cs_col_type the one
+ * place that answers "type / slot of column id c" — -1 when out of range or
+ * not projected */
 static int proj_of(const cstripe_scan *s, int32_t col)
 {
-    if (col < 0 || col >= (int32_t)s->r->head.column_count) return -1;
+    if (col < 0 || col >= (int32_t)cs_scan_ncols(s)) return -1;
     return s->gpu->proj_of_col[col];
 }
 
@@ -5160,6 +5614,7 @@ static int agg_grouped(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n
     for (uint32_t i = 0; i < n_group_cols; i++) {
         int pj = proj_of(s, (int32_t)group_cols[i]);
         if (pj < 0) { cs_set_err("group col %u not projected", group_cols[i]); return CSTRIPE_ERR_ARG; }
+        if (cs_col_derived(s, group_cols[i])) { cs_set_err("group col %u is a derived (lookup) column: scan_agg_grouped takes I8 or TEXT table columns; use scan_agg_hashed", group_cols[i]); return CSTRIPE_ERR_ARG; }
         if (r->cols[group_cols[i]].type != CSTRIPE_I8 &&
             r->cols[group_cols[i]].type != CSTRIPE_TEXT) { cs_set_err("group col %u must be I8 or TEXT", group_cols[i]); return CSTRIPE_ERR_ARG; }
         gp.gproj[i] = (uint32_t)pj;
@@ -5801,17 +6256,16 @@ int csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
 {
     if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
     cs_gpu_state *g = s->gpu;
-    cstripe_reader *r = s->r;
-    const uint32_t n_cols = r->head.column_count;
+    const uint32_t n_cols = cs_scan_ncols(s);
 
     SelectParams sp{};
     uint8_t widths[MAX_PROJ] = {0};
     uint32_t dst_col[MAX_PROJ] = {0};
     for (uint32_t c = 0; c < n_cols && out->col_values; c++) {
         if (!out->col_values[c]) continue;
-        const int pj = g->proj_of_col[c];
+        const int pj = proj_of(s, (int32_t)c);
         if (pj < 0) { cs_set_err("scan_select: column %u not projected", c); return CSTRIPE_ERR_ARG; }
-        widths[sp.n_cols] = (uint8_t)csf_type_width(r->cols[c].type);
+        widths[sp.n_cols] = (uint8_t)csf_type_width(cs_col_type(s, c));
         dst_col[sp.n_cols] = c;
         sp.cols[sp.n_cols].proj = (uint32_t)pj;
         sp.n_cols++;
@@ -6264,6 +6718,13 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
     auto set_range = [&](uint32_t k, uint32_t col, bool full, int64_t tlo, int64_t thi) {
         int64_t lo = 0, hi = 0;
         bool any = false;
+        uint32_t pl = 0;
+        if (const cs_lookup *lk = cs_col_lookup(s, col, &pl)) {
+            /* a derived column: the [min, max] of its payload array */
+            full = true;
+            tlo = lk->n ? lk->plo[pl] : 0;
+            thi = lk->n ? lk->phi[pl] : 0;
+        } else
         for (const cs_selchunk &sc : s->sel) {
             const csf_skipnode &nd = r->stripes[sc.stripe].nodes[col][sc.chunk].n;
             if (nd.has_min_max) {
@@ -6282,9 +6743,9 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
     for (uint32_t k = 0; k < n_key_cols; k++) {
         const uint32_t col = key_cols[k];
         const int pj = proj_of(s, (int32_t)col);
-        if (col >= r->head.column_count || pj < 0) { cs_set_err("scan_agg_hashed: key col %u not projected", col); return CSTRIPE_ERR_ARG; }
+        if (pj < 0) { cs_set_err("scan_agg_hashed: key col %u not projected", col); return CSTRIPE_ERR_ARG; }
         if (!out->keys[k] || !out->key_nulls[k]) { cs_set_err("scan_agg_hashed: no destination for key col %u", k); return CSTRIPE_ERR_ARG; }
-        const uint8_t t = r->cols[col].type;
+        const uint8_t t = cs_col_type(s, col);
         int64_t tlo, thi;
         switch (t) {
             case CSTRIPE_I8:   tlo = INT8_MIN;  thi = INT8_MAX;  break;
@@ -6861,7 +7322,7 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
     if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
     cs_gpu_state *g = s->gpu;
     cstripe_reader *r = s->r;
-    const uint32_t n_cols = r->head.column_count;
+    const uint32_t n_cols = cs_scan_ncols(s);
     if (!order || !out) { cs_set_err("scan_select_topn: bad args"); return CSTRIPE_ERR_ARG; }
     if (limit == 0 || limit > CSTRIPE_MAX_TOPN) {
         cs_set_err("scan_select_topn: limit %llu outside 1..%u",
@@ -6878,7 +7339,7 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
     uint8_t otype[CSTRIPE_MAX_ORDER_COLS] = {0};
     for (uint32_t k = 0; k < n_order; k++) {
         const uint32_t col = order[k].column;
-        if (col >= n_cols || g->proj_of_col[col] < 0) {
+        if (proj_of(s, (int32_t)col) < 0) {
             cs_set_err("scan_select_topn: order col %u not projected", col);
             return CSTRIPE_ERR_ARG;
         }
@@ -6891,7 +7352,7 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
             cs_set_err("scan_select_topn: order col %u: unknown flags 0x%x", col, order[k].flags);
             return CSTRIPE_ERR_ARG;
         }
-        const uint8_t t = r->cols[col].type;
+        const uint8_t t = cs_col_type(s, col);
         if (t == CSTRIPE_TEXT) {
             cs_set_err("scan_select_topn: order col %u is TEXT — its row-level order in this "
                        "ABI is whole-slot, not collation; order by a VARTEXT column instead", col);
@@ -6913,9 +7374,9 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
     uint32_t dst_col[MAX_PROJ] = {0};
     for (uint32_t c = 0; c < n_cols && out->col_values; c++) {
         if (!out->col_values[c]) continue;
-        const int pj = g->proj_of_col[c];
+        const int pj = proj_of(s, (int32_t)c);
         if (pj < 0) { cs_set_err("scan_select_topn: column %u not projected", c); return CSTRIPE_ERR_ARG; }
-        widths[sp.n_cols] = (uint8_t)csf_type_width(r->cols[c].type);
+        widths[sp.n_cols] = (uint8_t)csf_type_width(cs_col_type(s, c));
         dst_col[sp.n_cols] = c;
         sp.cols[sp.n_cols].proj = (uint32_t)pj;
         sp.n_cols++;
@@ -6940,7 +7401,12 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
         };
         uint64_t olo = 0, ohi = 0;
         bool any = false, full = false;
-        if (t == CSTRIPE_VARTEXT) {
+        uint32_t pl = 0;
+        if (const cs_lookup *lk = cs_col_lookup(s, col, &pl)) {
+            /* a derived column: the [min, max] of its payload array */
+            olo = ord_i(lk->n ? lk->plo[pl] : 0);
+            ohi = ord_i(lk->n ? lk->phi[pl] : 0);
+        } else if (t == CSTRIPE_VARTEXT) {
             /* dictionary ranks: exactly [0, n_dict - 1] */
             const int64_t nd = (int64_t)s->text_dicts[col].offsets.size() - 1;
             olo = ord_i(0);

@@ -1325,11 +1325,155 @@ extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t col
                                                  uint32_t n_text_consts,
                                                  const cstripe_value_set *sets, uint32_t n_sets)
 {
+    return cstripe_scan_begin_lookups(r, cols_mask, preds, n_preds, text_consts, n_text_consts,
+                                      sets, n_sets, nullptr, 0);
+}
+
+/* validate and copy the lookups of a scan (no device work before every
+ * argument check has passed); false with the message set */
+static bool lookups_begin(cstripe_scan *s, const cstripe_lookup *lookups, uint32_t n_lookups)
+{
+    cstripe_reader *r = s->r;
+    if (n_lookups > CSTRIPE_MAX_LOOKUPS) { cs_set_err("scan_begin_lookups: %u lookups (max %d)", n_lookups, CSTRIPE_MAX_LOOKUPS); return false; }
+    if (n_lookups && !lookups) { cs_set_err("scan_begin_lookups: %u lookups but no array", n_lookups); return false; }
+    uint32_t next_col = r->head.column_count;
+    s->lookups.resize(n_lookups);
+    for (uint32_t l = 0; l < n_lookups; l++) {
+        const cstripe_lookup &in = lookups[l];
+        cs_lookup &lk = s->lookups[l];
+        if (in.n_payloads == 0 || in.n_payloads > CSTRIPE_MAX_LOOKUP_PAYLOADS) {
+            cs_set_err("scan_begin_lookups: lookup %u has %u payloads (1..%d)", l, in.n_payloads, CSTRIPE_MAX_LOOKUP_PAYLOADS);
+            return false;
+        }
+        if (in.n > CSTRIPE_MAX_SET_VALUES) {
+            cs_set_err("scan_begin_lookups: lookup %u holds %llu entries (max %llu)", l,
+                       (unsigned long long)in.n, (unsigned long long)CSTRIPE_MAX_SET_VALUES);
+            return false;
+        }
+        if (in.flags & ~CSTRIPE_LOOKUP_INNER) { cs_set_err("scan_begin_lookups: lookup %u: unknown flags 0x%x", l, in.flags); return false; }
+        if (in.n && !in.keys) { cs_set_err("scan_begin_lookups: lookup %u has %llu entries but no keys", l, (unsigned long long)in.n); return false; }
+        for (uint32_t p = 0; p < in.n_payloads; p++)
+            if (in.n && !in.payloads[p]) {
+                cs_set_err("scan_begin_lookups: lookup %u has %llu entries but payload %u is NULL", l, (unsigned long long)in.n, p);
+                return false;
+            }
+        if (in.key_column >= r->head.column_count) {
+            cs_set_err("scan_begin_lookups: lookup %u: key column %u out of range", l, in.key_column);
+            return false;
+        }
+        const uint8_t kt = r->cols[in.key_column].type;
+        if (kt != CSTRIPE_I8 && kt != CSTRIPE_I16 && kt != CSTRIPE_I32 && kt != CSTRIPE_I64) {
+            cs_set_err("scan_begin_lookups: lookup %u: key column %u must be I8/I16/I32/I64", l, in.key_column);
+            return false;
+        }
+        if (next_col + in.n_payloads > 64) {
+            cs_set_err("scan_begin_lookups: lookup %u: table plus derived columns exceed 64", l);
+            return false;
+        }
+        lk.key_column = in.key_column;
+        lk.n_payloads = in.n_payloads;
+        lk.first_col = next_col;
+        next_col += in.n_payloads;
+        lk.inner = (in.flags & CSTRIPE_LOOKUP_INNER) != 0;
+        lk.on_device = in.on_device != 0 && in.n != 0;
+        lk.n = in.n;
+    }
+    s->n_derived = next_col - r->head.column_count;
+    /* host maps: copies, duplicate check, ranges */
+    for (uint32_t l = 0; l < n_lookups; l++) {
+        const cstripe_lookup &in = lookups[l];
+        cs_lookup &lk = s->lookups[l];
+        if (lk.on_device || !lk.n) continue;
+        lk.keys.assign(in.keys, in.keys + in.n);
+        lk.sorted_keys = lk.keys;
+        std::sort(lk.sorted_keys.begin(), lk.sorted_keys.end());
+        for (size_t i = 1; i < lk.sorted_keys.size(); i++)
+            if (lk.sorted_keys[i] == lk.sorted_keys[i - 1]) {
+                cs_set_err("scan_begin_lookups: lookup %u: duplicate build key %lld (build keys must be distinct)",
+                           l, (long long)lk.sorted_keys[i]);
+                return false;
+            }
+        lk.klo = lk.sorted_keys.front();
+        lk.khi = lk.sorted_keys.back();
+        for (uint32_t p = 0; p < lk.n_payloads; p++) {
+            lk.payloads[p].assign(in.payloads[p], in.payloads[p] + in.n);
+            const auto mm = std::minmax_element(lk.payloads[p].begin(), lk.payloads[p].end());
+            lk.plo[p] = *mm.first;
+            lk.phi[p] = *mm.second;
+        }
+    }
+    return true;
+}
+
+/* device maps: one reduction launch per array; after every argument check */
+static bool lookups_begin_device(cstripe_scan *s, const cstripe_lookup *lookups)
+{
+    for (size_t l = 0; l < s->lookups.size(); l++) {
+        cs_lookup &lk = s->lookups[l];
+        if (!lk.on_device) continue;
+        const cstripe_lookup &in = lookups[l];
+        lk.dev_keys = in.keys;
+        if (csgpu_set_range(in.keys, in.n, &lk.klo, &lk.khi, &lk.dev_id) != CSTRIPE_OK) return false;
+        for (uint32_t p = 0; p < lk.n_payloads; p++) {
+            int dev = -1;
+            lk.dev_payloads[p] = in.payloads[p];
+            if (csgpu_set_range(in.payloads[p], in.n, &lk.plo[p], &lk.phi[p], &dev) != CSTRIPE_OK) return false;
+            if (dev != lk.dev_id) {
+                cs_set_err("scan_begin_lookups: lookup %u: payload %u lives on device %d, the keys on device %d",
+                           (unsigned)l, p, dev, lk.dev_id);
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+/* `key_column IN keys` refutation of one lookup over a chunk's [min, max] */
+static bool lookup_refutes(const cs_lookup &lk, const csf_skipnode &nd)
+{
+    if (!nd.has_min_max) return false;
+    if (lk.n == 0) return true;
+    if (lk.on_device) return lk.khi < nd.min_i || lk.klo > nd.max_i;
+    auto it = std::lower_bound(lk.sorted_keys.begin(), lk.sorted_keys.end(), nd.min_i);
+    return it == lk.sorted_keys.end() || *it > nd.max_i;
+}
+
+extern "C" cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t cols_mask,
+                                                    const cstripe_pred *preds, uint32_t n_preds,
+                                                    const cstripe_text_const *text_consts,
+                                                    uint32_t n_text_consts,
+                                                    const cstripe_value_set *sets, uint32_t n_sets,
+                                                    const cstripe_lookup *lookups, uint32_t n_lookups)
+{
     if (!r) { cs_set_err("scan_begin: null reader"); return nullptr; }
     auto *s = new cstripe_scan();
     s->r = r;
     s->cols_mask = cols_mask;
     if (n_preds > CSTRIPE_MAX_PREDS) { cs_set_err("too many predicates (max %d)", CSTRIPE_MAX_PREDS); delete s; return nullptr; }
+    if (!lookups_begin(s, lookups, n_lookups)) { delete s; return nullptr; }
+    {
+        uint32_t n_inner = 0;
+        for (const cs_lookup &lk : s->lookups) n_inner += lk.inner ? 1 : 0;
+        if (n_preds + n_inner > CSTRIPE_MAX_PREDS) {
+            cs_set_err("scan_begin_lookups: %u predicates plus %u INNER lookups exceed the %d predicates of one scan",
+                       n_preds, n_inner, CSTRIPE_MAX_PREDS);
+            delete s; return nullptr;
+        }
+    }
+    /* predicates naming a derived column: checked before any device work */
+    for (uint32_t i = 0; i < n_preds; i++) {
+        if (preds[i].column < r->head.column_count) continue;
+        if (preds[i].column >= cs_scan_ncols(s)) {
+            cs_set_err("scan_begin: predicate %u: column %u out of range (%u table + %u derived columns)",
+                       i, preds[i].column, r->head.column_count, s->n_derived);
+            delete s; return nullptr;
+        }
+        if (preds[i].op > CSTRIPE_PRED_NE) {
+            cs_set_err("scan_begin_lookups: predicate %u: op %u on derived column %u is not supported "
+                       "(LT..NE only; no IN / NOT IN)", i, preds[i].op, preds[i].column);
+            delete s; return nullptr;
+        }
+    }
     if (n_sets > CSTRIPE_MAX_SETS) { cs_set_err("scan_begin_sets: %u value sets (max %d)", n_sets, CSTRIPE_MAX_SETS); delete s; return nullptr; }
     if (n_sets && !sets) { cs_set_err("scan_begin_sets: %u value sets but no array", n_sets); delete s; return nullptr; }
     for (uint32_t i = 0; i < n_text_consts; i++) {
@@ -1368,8 +1512,17 @@ extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t col
             vs.vals.erase(std::unique(vs.vals.begin(), vs.vals.end()), vs.vals.end());
         }
     }
+    if (!lookups_begin_device(s, lookups)) { delete s; return nullptr; }
     for (uint32_t i = 0; i < n_preds; i++) {
-        if (preds[i].column >= r->cols.size()) { cs_set_err("pred column out of range"); delete s; return nullptr; }
+        if (preds[i].column >= cs_scan_ncols(s)) { cs_set_err("pred column out of range"); delete s; return nullptr; }
+        if (cs_col_derived(s, preds[i].column)) {
+            /* an ordinary integer atom over a derived (I64) column, checked
+             * above; it has no cols_mask bit */
+            s->preds.push_back(preds[i]);
+            if (s->preds.back().or_group == 0)
+                s->preds.back().or_group = 0xFFFFFF00u + i;
+            continue;
+        }
         if (preds[i].op > CSTRIPE_PRED_NOT_IN) { cs_set_err("scan_begin: predicate %u has unknown op %u", i, preds[i].op); delete s; return nullptr; }
         if (pred_is_set(preds[i])) {
             const uint8_t t = r->cols[preds[i].column].type;
@@ -1406,6 +1559,19 @@ extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t col
         if (s->preds.back().or_group == 0)
             s->preds.back().or_group = 0xFFFFFF00u + i;   /* private ids */
         s->cols_mask |= 1ull << preds[i].column;   /* pred columns must be read */
+    }
+    /* lookups: key columns are read; INNER is the standalone conjunct
+     * "derived column 0 IS NOT NULL", the atom GE INT64_MIN */
+    for (size_t l = 0; l < s->lookups.size(); l++) {
+        const cs_lookup &lk = s->lookups[l];
+        s->cols_mask |= 1ull << lk.key_column;
+        if (!lk.inner) continue;
+        cstripe_pred q{};
+        q.column = lk.first_col;
+        q.op = CSTRIPE_PRED_GE;
+        q.ival = INT64_MIN;
+        q.or_group = 0xFFFFFF00u + n_preds + (uint32_t)l;
+        s->preds.push_back(q);
     }
     /* contiguous groups (stable: original order kept within a group) */
     std::stable_sort(s->preds.begin(), s->preds.end(),
@@ -1445,8 +1611,9 @@ extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t col
                                   * EQ/NE only; kernel not taught the
                                   * transform) */
         for (const auto &p : s->preds)
-            any_text |= r->cols[p.column].type == CSTRIPE_TEXT ||
-                        r->cols[p.column].type == CSTRIPE_VARTEXT;
+            any_text |= cs_col_type(s, p.column) == CSTRIPE_TEXT ||
+                        cs_col_type(s, p.column) == CSTRIPE_VARTEXT ||
+                        cs_col_derived(s, p.column);   /* nor about lookups */
         any_text |= any_set;     /* nor about value sets */
         std::vector<uint8_t> selmask;
         if (!s->preds.empty() && !any_text && dpv != 0 &&
@@ -1477,9 +1644,22 @@ extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t col
             while (i < s->preds.size() && selected) {
                 size_t j = i;
                 bool group_refuted = true;
+                /* atoms on derived columns: never refuted by value; a group
+                 * made only of them, all of ONE lookup, is refuted exactly
+                 * when `key_column IN keys` is */
+                const cs_lookup *g_lk = nullptr;
+                bool g_only_lk = true;
                 while (j < s->preds.size() &&
                        s->preds[j].or_group == s->preds[i].or_group) {
                     const cstripe_pred &p = s->preds[j];
+                    if (cs_col_derived(s, p.column)) {
+                        const cs_lookup *lk = cs_col_lookup(s, p.column, nullptr);
+                        if (g_lk && g_lk != lk) g_only_lk = false;
+                        g_lk = lk;
+                        j++;
+                        continue;
+                    }
+                    g_only_lk = false;
                     const csf_skipnode &nd = st.nodes[p.column][k].n;
                     /* all-NULL chunks have no min/max and are never refuted
                      * (columnar_reader.c:1160-1166) */
@@ -1516,6 +1696,9 @@ extern "C" cstripe_scan *cstripe_scan_begin_sets(cstripe_reader *r, uint64_t col
                         group_refuted = false;
                     j++;
                 }
+                if (g_lk)
+                    group_refuted = g_only_lk &&
+                                    lookup_refutes(*g_lk, st.nodes[g_lk->key_column][k].n);
                 if (group_refuted) selected = false;
                 i = j;
             }
@@ -1584,6 +1767,27 @@ extern "C" int cstripe_scan_last_set_ms(const cstripe_scan *s, double *build_ms,
     if (build_ms) *build_ms = s->last_set_build_ms;
     if (probe_ms) *probe_ms = s->last_set_probe_ms;
     return CSTRIPE_OK;
+}
+
+extern "C" uint32_t cstripe_scan_column_count(const cstripe_scan *s)
+{
+    return s ? cs_scan_ncols(s) : 0;
+}
+
+extern "C" int cstripe_scan_last_lookup_ms(const cstripe_scan *s, double *build_ms, double *probe_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (build_ms) *build_ms = s->last_lookup_build_ms;
+    if (probe_ms) *probe_ms = s->last_lookup_probe_ms;
+    return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_lookup_form(const cstripe_scan *s, uint32_t lookup_idx, uint64_t *size)
+{
+    if (!s || lookup_idx >= s->lookups.size()) { cs_set_err("scan_lookup_form: lookup %u is not a lookup of this scan", lookup_idx); return CSTRIPE_ERR_ARG; }
+    const bool staged = s->gpu != nullptr;
+    if (size) *size = staged ? s->lookups[lookup_idx].form_size : 0;
+    return staged ? s->lookups[lookup_idx].form : CSTRIPE_LOOKUP_FORM_NONE;
 }
 
 extern "C" int cstripe_scan_set_form(const cstripe_scan *s, uint32_t set_idx, uint64_t *size)

@@ -77,10 +77,35 @@ struct cs_value_set {
     uint64_t form_size = 0;              /* slots or bits */
 };
 
+/* one lookup (cstripe_scan_begin_lookups): the build side of an N:1 join */
+struct cs_lookup {
+    uint32_t key_column = 0;
+    uint32_t n_payloads = 0;
+    uint32_t first_col = 0;              /* column id of payload 0 */
+    bool inner = false;
+    bool on_device = false;
+    uint64_t n = 0;
+    std::vector<int64_t> keys;           /* host map: as given (entry order) */
+    std::vector<int64_t> sorted_keys;    /* host map: sorted copy (refutation) */
+    std::vector<int64_t> payloads[CSTRIPE_MAX_LOOKUP_PAYLOADS];
+    const int64_t *dev_keys = nullptr;   /* device map: the caller's pointers */
+    const int64_t *dev_payloads[CSTRIPE_MAX_LOOKUP_PAYLOADS] = {};
+    int dev_id = -1;                     /* device that owns them */
+    int64_t klo = 0, khi = 0;            /* [min, max] of the keys, n > 0 */
+    int64_t plo[CSTRIPE_MAX_LOOKUP_PAYLOADS] = {};   /* per payload [min, max] */
+    int64_t phi[CSTRIPE_MAX_LOOKUP_PAYLOADS] = {};
+    int form = 0;                        /* CSTRIPE_LOOKUP_FORM_* at the last stage */
+    uint64_t form_size = 0;
+};
+
 struct cstripe_scan {
     cstripe_reader *r = nullptr;
     uint64_t cols_mask = 0;
     std::vector<cstripe_pred> preds;
+    std::vector<cs_lookup> lookups;
+    uint32_t n_derived = 0;                 /* payload columns of all lookups */
+    double last_lookup_build_ms = 0.0;      /* stage-time lookup split */
+    double last_lookup_probe_ms = 0.0;
     std::vector<cs_value_set> sets;         /* IN / NOT_IN preds: ival indexes these */
     /* [pred]: sorted chunk-refutation keys of a TEXT (lex keys) or VARTEXT
      * (prefix keys) set predicate; integer columns use sets[].vals */
@@ -119,6 +144,32 @@ struct cstripe_scan {
     uint32_t rr_rows = 0;
     uint64_t rr_first = 0;
 };
+
+/* Column addressing of a scan: ids below the table's column count are table
+ * columns, the ids after them the derived (lookup payload) columns, I64. */
+static inline uint32_t cs_scan_ncols(const cstripe_scan *s)
+{
+    return s->r->head.column_count + s->n_derived;
+}
+static inline bool cs_col_derived(const cstripe_scan *s, uint32_t c)
+{
+    return c >= s->r->head.column_count && c < cs_scan_ncols(s);
+}
+/* type of column id c (c < cs_scan_ncols) */
+static inline uint8_t cs_col_type(const cstripe_scan *s, uint32_t c)
+{
+    return c < s->r->head.column_count ? s->r->cols[c].type : (uint8_t)CSTRIPE_I64;
+}
+/* lookup that owns derived column c; *payload gets its payload index */
+static inline const cs_lookup *cs_col_lookup(const cstripe_scan *s, uint32_t c, uint32_t *payload)
+{
+    for (const cs_lookup &lk : s->lookups)
+        if (c >= lk.first_col && c < lk.first_col + lk.n_payloads) {
+            if (payload) *payload = c - lk.first_col;
+            return &lk;
+        }
+    return nullptr;
+}
 
 /* implemented in cstripe_gpu.hip */
 /* device chunk-group pruning (SelectedChunkMask on GPU):

@@ -477,6 +477,114 @@ int cstripe_scan_last_set_ms(const cstripe_scan *s, double *build_ms, double *pr
 #define CSTRIPE_SET_FORM_HASH   1
 #define CSTRIPE_SET_FORM_BITMAP 2
 int cstripe_scan_set_form(const cstripe_scan *s, uint32_t set_idx, uint64_t *size);
+
+/* ---- lookups: the device N:1 join with payload columns ----
+ * A lookup joins the scanned table to a build side (key -> payload values)
+ * as a LEFT JOIN whose build keys are distinct: the FK -> PK joins a
+ * co-located or reference-table plan pushes to every worker. Each payload
+ * becomes a DERIVED COLUMN of the scan that every query surface addresses by
+ * a column id past the table's own. */
+#define CSTRIPE_MAX_LOOKUPS          2
+#define CSTRIPE_MAX_LOOKUP_PAYLOADS  4
+#define CSTRIPE_LOOKUP_INNER         1u   /* flags: drop rows without a match */
+
+typedef struct cstripe_lookup {
+    uint32_t        key_column;   /* I8/I16/I32/I64 column of the scanned table */
+    uint32_t        n_payloads;   /* 1..CSTRIPE_MAX_LOOKUP_PAYLOADS */
+    const int64_t  *keys;         /* n build keys, all distinct, no NULLs */
+    const int64_t  *payloads[CSTRIPE_MAX_LOOKUP_PAYLOADS];  /* n entries each, parallel to keys */
+    uint64_t        n;            /* 0 legal; <= CSTRIPE_MAX_SET_VALUES */
+    uint32_t        on_device;    /* keys AND payloads are device memory, read in place */
+    uint32_t        flags;        /* CSTRIPE_LOOKUP_* */
+} cstripe_lookup;
+
+/* scan_begin_lookups: scan_begin_sets plus lookups. With n_lookups == 0 it is
+ * exactly cstripe_scan_begin_sets (which calls it).
+ *  - Derived columns: payload p of lookup l is column
+ *    cstripe_column_count(r) + (payloads of the lookups before l) + p, type
+ *    I64. It is always projected (it has no cols_mask bit) and takes one of
+ *    the 16 projected slots of a scan; overflow is CSTRIPE_ERR_ARG from
+ *    cstripe_gpu_stage and leaves the scan unstaged. Table plus derived
+ *    columns must stay <= 64. The key column is projected implicitly.
+ *  - Row semantics: derived column d of a row is payload[e] when the row's key
+ *    is non-NULL and equals build key e; NULL otherwise. A key value outside
+ *    an I8/I16/I32 key column's range never matches. CSTRIPE_LOOKUP_INNER adds
+ *    one standalone conjunct "derived column 0 of this lookup IS NOT NULL"
+ *    (the atom GE INT64_MIN); it counts against CSTRIPE_MAX_PREDS.
+ *  - A derived id is accepted as the predicate column of LT..NE (a NULL
+ *    operand fails the atom, so a standalone predicate on a derived column
+ *    gives inner-join semantics), as the operand of COUNT_COL and every I64
+ *    aggregate kind, as a cstripe_scan_agg_hashed key, as a
+ *    cstripe_scan_select_topn order column, and as a wanted column of
+ *    cstripe_scan_select / _select_topn: for a scan with lookups the
+ *    per-column arrays of cstripe_rows have cstripe_scan_column_count(s)
+ *    entries. Not accepted (CSTRIPE_ERR_ARG / NULL, message set): IN / NOT_IN
+ *    on a derived column, cstripe_scan_agg_grouped keys, a TEXT / VARTEXT /
+ *    float key column. cstripe_scan_next_batch and cstripe_read_row do not
+ *    know derived columns; their arrays stay cstripe_column_count(r) long.
+ *  - Key packing (hashed GROUP BY, top-N): a derived column's [lo, hi] is the
+ *    [min, max] of its payload array, computed at begin (one reduction launch
+ *    per device array). A value outside it is a device array that changed
+ *    after begin: the call fails with CSTRIPE_ERR_FORMAT.
+ *  - Memory: host arrays are copied at begin. Device arrays (on_device != 0)
+ *    are read in place at every stage and must stay valid until
+ *    cstripe_scan_end, on the device the scan is staged on (else
+ *    CSTRIPE_ERR_ARG at stage). The keys must not change; payload values may
+ *    change between stages within their begin-time range.
+ *  - Errors at begin (NULL, message set): n_lookups > CSTRIPE_MAX_LOOKUPS,
+ *    n_payloads 0 or > 4, a NULL array with n > 0, n above the limit, a bad
+ *    key column or key type, a predicate naming a column beyond
+ *    cstripe_scan_column_count, too many predicates with the INNER atoms, and
+ *    duplicate build keys in a host map (the message names the key).
+ *    Duplicates in a device map are found by the build kernel at stage:
+ *    cstripe_gpu_stage returns CSTRIPE_ERR_ARG naming the lookup and the scan
+ *    stays unstaged.
+ *  - Chunk refutation (host loop; the device prune kernel is skipped when a
+ *    predicate names a derived column): an atom on a derived column never
+ *    refutes by value. An or_group whose members are all atoms on derived
+ *    columns of ONE lookup refutes a chunk exactly when `key_column IN keys`
+ *    would: for a host map no build key lies in the key column's [min, max];
+ *    for a device map the key range misses it. Mixed with other columns it
+ *    never refutes. All-NULL key chunks (no min/max) survive.
+ *  - Device evaluation: all at cstripe_gpu_stage, after the value sets; no
+ *    query kernel knows about lookups. One table per lookup maps key -> entry
+ *    index: a direct u32 array over [lo, hi] when hi - lo + 1 <=
+ *    max(2^16, 4 n) and < 2^32, else an open-addressing hash table of
+ *    max(2, next_pow2(2 n)) slots. A probe kernel writes each derived
+ *    column's exists bitmap, a scan kernel its rank table, a gather kernel
+ *    its compacted values; the column then reads as an ordinary sparse I64
+ *    column in scratch. Such scans report CSTRIPE_AGG_PATH_GENERAL.
+ *    CSTRIPE_LOOKUP_FORM=hash|direct (environment, read per stage) forces the
+ *    form; a forced direct over an illegal range falls back to hash. Results
+ *    never depend on it. It is a switch for tests and measurements: a forced
+ *    direct table takes 4 B per value of [lo, hi], whatever n is.
+ *    Probe, rank scan and gather run over batches of chunk groups of at most
+ *    2^26 rows (CSTRIPE_LOOKUP_BATCH_ROWS overrides it), which bounds the
+ *    stage's temporary memory at 256 MB plus the uploaded copy of a host map.
+ *  - Out of scope: float / TEXT / VARTEXT payloads and keys, N:M joins
+ *    (duplicate build keys), composite keys, derived columns in next_batch /
+ *    read_row, a dense fast path when every row matches, exact device-side
+ *    pruning for device maps, multi-GPU distribution of the build side. */
+cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t cols_mask,
+                                         const cstripe_pred *preds, uint32_t n_preds,
+                                         const cstripe_text_const *text_consts,
+                                         uint32_t n_text_consts,
+                                         const cstripe_value_set *sets, uint32_t n_sets,
+                                         const cstripe_lookup *lookups, uint32_t n_lookups);
+/* table columns + derived columns of the scan */
+uint32_t cstripe_scan_column_count(const cstripe_scan *s);
+/* device time (hipEvents, milliseconds) of the last cstripe_gpu_stage's lookup
+ * work, all lookups together: table build (clear + insert kernel; a host
+ * map's upload is not in it), probe (bitmap, rank scan, gather). Both 0
+ * without a lookup. Any out pointer may be NULL. */
+int cstripe_scan_last_lookup_ms(const cstripe_scan *s, double *build_ms, double *probe_ms);
+/* form of lookup lookup_idx's table at the last stage: 0 none / unstaged,
+ * 1 hash, 2 direct; *size (may be NULL) gets its slots or entries.
+ * CSTRIPE_ERR_ARG when lookup_idx is not a lookup of this scan. */
+#define CSTRIPE_LOOKUP_FORM_NONE   0
+#define CSTRIPE_LOOKUP_FORM_HASH   1
+#define CSTRIPE_LOOKUP_FORM_DIRECT 2
+int cstripe_scan_lookup_form(const cstripe_scan *s, uint32_t lookup_idx, uint64_t *size);
 void cstripe_scan_end(cstripe_scan *s);
 int64_t cstripe_scan_chunk_groups_filtered(const cstripe_scan *s);
 
