@@ -224,6 +224,22 @@ class HGroups(C.Structure):
                 ("partials", C.c_void_p)]
 
 
+MAX_GROUP_ORDER = 4
+MAX_HAVING = 4
+GORDER_AGG = 0                   # index = position in aggs
+GORDER_KEY = 1                   # index = position in key_cols
+
+
+class GroupOrder(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+class Having(C.Structure):
+    _fields_ = [("agg", C.c_uint32), ("op", C.c_uint32), ("ival", C.c_int64),
+                ("fval", C.c_double)]
+
+
 def partial_dtype():
     """numpy structured dtype mirroring cstripe_partial (40 bytes)"""
     import numpy as np
@@ -347,6 +363,16 @@ _scan_agg_hashed = _sig("cstripe_scan_agg_hashed", C.c_int,
 _last_hash_ms = _sig("cstripe_scan_last_hash_ms", C.c_int,
                      [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                       C.POINTER(C.c_double)])
+_scan_agg_hashed_topn = _sig("cstripe_scan_agg_hashed_topn", C.c_int,
+                             [C.c_void_p, C.POINTER(AggSpec), C.c_uint32,
+                              C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64,
+                              C.POINTER(Having), C.c_uint32,
+                              C.POINTER(GroupOrder), C.c_uint32, C.c_uint64,
+                              C.POINTER(HGroups)])
+_last_group_topn = _sig("cstripe_scan_last_group_topn", C.c_int,
+                        [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                         C.POINTER(C.c_double), C.POINTER(C.c_double),
+                         C.POINTER(C.c_double)])
 _combine_groups = _sig("cagg_combine_groups", C.c_int,
                        [C.POINTER(AggSpec), C.c_uint32, C.c_uint32,
                         C.POINTER(HGroups), C.c_uint32, C.POINTER(HGroups),
@@ -818,6 +844,139 @@ def combine_groups(aggs, n_key_cols, results, capacity=None):
     return _hgroups_result(bufs, hg.n_groups)
 
 
+def parse_group_order(order):
+    """[(kind, index, flags)] from items like ("agg", 0, "desc"), ("key", 1)
+    or ("agg", 2, "desc", "nulls_first"). Direction defaults to ascending and
+    NULLs to last; both flags are taken literally, as the C ABI takes them."""
+    out = []
+    for o in order:
+        o = tuple(o)
+        if len(o) < 2 or str(o[0]).lower() not in ("agg", "key"):
+            raise CStripeError(f"group order entry {o!r}: want ('agg'|'key', index, ...)")
+        flags = 0
+        for opt in o[2:]:
+            opt = str(opt).lower()
+            if opt == "desc":
+                flags |= ORDER_DESC
+            elif opt == "nulls_first":
+                flags |= ORDER_NULLS_FIRST
+            elif opt not in ("asc", "nulls_last"):
+                raise CStripeError(f"group order entry {o!r}: unknown option {opt!r}")
+        out.append((GORDER_AGG if str(o[0]).lower() == "agg" else GORDER_KEY,
+                    int(o[1]), flags))
+    return out
+
+
+def make_group_order(order):
+    terms = parse_group_order(order)
+    arr = (GroupOrder * max(1, len(terms)))()
+    for i, (kind, index, flags) in enumerate(terms):
+        arr[i].kind, arr[i].index, arr[i].flags = kind, index, flags
+    return arr, len(terms)
+
+
+def make_having(having):
+    """having: list of (agg_index, PRED_LT..PRED_NE, value). The value goes
+    into both constants: ival (COUNT and integer kinds) when it is integral,
+    fval (f64 kinds) always."""
+    import math
+    arr = (Having * max(1, len(having)))()
+    for i, (agg, op, value) in enumerate(having):
+        arr[i].agg, arr[i].op = agg, op
+        arr[i].fval = float(value)
+        if not isinstance(value, float):
+            arr[i].ival = int(value)
+        elif math.isfinite(value) and value == int(value):
+            arr[i].ival = int(value)
+    return arr, len(having)
+
+
+_F64_KINDS = (AGG_SUM_F64, AGG_MIN_F64, AGG_MAX_F64)
+_COUNT_KINDS = (AGG_COUNT_STAR, AGG_COUNT_COL)
+
+
+def _f64_ord(x):
+    """order-preserving int of a float under PG order: NaN greatest and equal
+    to itself, -0.0 = +0.0 (topn_f64_ord of the library)"""
+    import struct
+    x = float(x)
+    if x != x:
+        return 0xFFF0000000000001
+    u = struct.unpack("<Q", struct.pack("<d", x))[0]
+    if u == 1 << 63:
+        u = 0
+    return (~u & ((1 << 64) - 1)) if u >> 63 else (u | (1 << 63))
+
+
+def _partial_value(kind, p):
+    """(is_null, comparable Python int) of one aggregate's final value"""
+    if kind in _COUNT_KINDS:
+        return False, int(p["count"])
+    if p["is_null"]:
+        return True, 0
+    if kind in _F64_KINDS:
+        return False, _f64_ord(p["f64"])
+    return False, partial_i128(p)
+
+
+def merge_groups_topn(aggs, n_key_cols, results, order, limit, offset=0, having=()):
+    """The coordinator side of GROUP BY ... HAVING ... ORDER BY ... LIMIT over
+    per-shard agg_hashed() / agg_hashed_topn() results (host only):
+    combine_groups, then HAVING on the merged values, then the total order of
+    agg_hashed_topn (order terms, ties ascending by key tuple, NULL keys
+    last), then rows [offset, offset + limit). Returns the agg_hashed dict.
+
+    What the reference's planner says holds here too
+    (multi_logical_optimizer.c:5039-5140, :2650-2682): a per-shard top-N with
+    the exact limit + offset, and a per-shard HAVING, are exact only when the
+    shards' groups are DISJOINT — the GROUP BY holds the partition column, so
+    every group is complete on its shard. Otherwise a worker limit is an
+    approximation (a group outside every shard's top-N may still win after
+    the merge), and HAVING belongs after the merge: pass the shards' full
+    agg_hashed() results and give `having` here."""
+    if limit < 0 or offset < 0:
+        raise CStripeError("merge_groups_topn: limit and offset must be >= 0")
+    terms = parse_group_order(order)
+    kinds = [tuple(a)[0] for a in aggs]
+    for kind, index, _ in terms:
+        if index < 0 or index >= (len(aggs) if kind == GORDER_AGG else n_key_cols):
+            raise CStripeError(f"merge_groups_topn: order index {index} out of range")
+    res = combine_groups(aggs, n_key_cols, list(results))
+    n = int(res["n_groups"])
+    parts = res["partials"]
+
+    def survives(g):
+        for agg, op, value in having:
+            null, v = _partial_value(kinds[agg], parts[g, agg])
+            if null:
+                return False
+            c = _f64_ord(value) if kinds[agg] in _F64_KINDS else value
+            if not ((v < c), (v <= c), (v > c), (v >= c), (v == c), (v != c))[op]:
+                return False
+        return True
+
+    def sort_key(g):
+        key = []
+        for kind, index, flags in terms:
+            if kind == GORDER_AGG:
+                null, v = _partial_value(kinds[index], parts[g, index])
+            else:
+                null, v = bool(res["key_nulls"][index][g]), int(res["keys"][index][g])
+            if null:
+                key.append((0 if flags & ORDER_NULLS_FIRST else 2, 0))
+            else:
+                key.append((1, -v if flags & ORDER_DESC else v))
+        return tuple(key) + (g,)          # combine_groups' order breaks ties
+
+    idx = sorted((g for g in range(n) if survives(g)), key=sort_key)
+    import numpy as np
+    idx = np.array(idx[offset:offset + limit], dtype=np.int64)
+    return {"n_groups": len(idx),
+            "keys": [a[idx] for a in res["keys"]],
+            "key_nulls": [a[idx] for a in res["key_nulls"]],
+            "partials": parts[idx]}
+
+
 def parse_order(order):
     """[(col, desc, nulls_first)] from a list of col, (col, "asc"|"desc") or
     (col, dir, "first"|"last"); NULL placement defaults to PG's: ascending
@@ -1145,6 +1304,42 @@ class Scan:
                 for k, c in enumerate(key_cols)
                 if self._col_type(c) == VARTEXT}
         return res
+
+    def agg_hashed_topn(self, aggs, key_cols, capacity, order, limit, having=(),
+                        decode_text=False):
+        """GROUP BY ... [HAVING] ORDER BY ... LIMIT on the device
+        (cstripe_scan_agg_hashed_topn): the groups of agg_hashed(aggs,
+        key_cols, capacity), filtered by `having` — items (agg_index,
+        ca.PRED_GT, value), ANDed — ordered by `order` — items like
+        ("agg", 0, "desc") and ("key", 1), with an optional "nulls_first";
+        ties ascending by key tuple — and cut to `limit`. Only those groups
+        are copied back. Returns the agg_hashed dict in the requested order."""
+        arr = make_aggs(aggs)
+        kc = (C.c_uint32 * max(1, len(key_cols)))(*key_cols)
+        oarr, n_order = make_group_order(order)
+        harr, n_having = make_having(having)
+        bufs, hg = _alloc_hgroups(len(key_cols), len(aggs),
+                                  min(max(int(limit), 1), MAX_TOPN))
+        _check(_scan_agg_hashed_topn(self._h, arr, len(aggs), kc, len(key_cols),
+                                     capacity, harr, n_having, oarr, n_order,
+                                     limit, C.byref(hg)), "scan_agg_hashed_topn")
+        res = _hgroups_result(bufs, hg.n_groups)
+        if decode_text:
+            res["text_keys"] = {
+                k: self._decode_ranks(c, res["keys"][k], res["key_nulls"][k])
+                for k, c in enumerate(key_cols)
+                if self._col_type(c) == VARTEXT}
+        return res
+
+    @property
+    def last_group_topn(self):
+        """(groups before HAVING, groups kept, range ms, select ms, emit ms)
+        of the last agg_hashed_topn call"""
+        n, k = C.c_uint64(), C.c_uint64()
+        r, s, e = C.c_double(), C.c_double(), C.c_double()
+        _check(_last_group_topn(self._h, C.byref(n), C.byref(k), C.byref(r),
+                                C.byref(s), C.byref(e)), "scan_last_group_topn")
+        return n.value, k.value, r.value, s.value, e.value
 
     @property
     def last_hash_ms(self):

@@ -163,6 +163,17 @@ struct cs_gpu_state {
     unsigned long long *d_hcount = nullptr;    /* one word: occupied slots */
     uint64_t hkeys_slots = 0, hcells_n = 0, hokeys_n = 0, hocells_n = 0;
     hipEvent_t hev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    /* scan_agg_hashed_topn: indices of the groups HAVING kept, their order
+     * and tie words, the state block, two radix-select states (order word,
+     * tie word) and the limit-sized gather buffer. Grow-only. */
+    uint32_t *d_gt_kept = nullptr;      /* [capacity] indices into d_hokeys */
+    uint64_t *d_gt_ord = nullptr;       /* [capacity] order word per kept group */
+    uint64_t *d_gt_tie = nullptr;       /* [capacity] tie word per kept group */
+    struct GtopnState *d_gt_state = nullptr;
+    struct TopnState *d_gt_sel = nullptr;   /* [2] */
+    uint8_t *d_gt_out = nullptr;        /* limit * (24 + 32 * n_aggs) bytes */
+    uint64_t gt_kept_n = 0, gt_ord_n = 0, gt_tie_n = 0, gt_out_bytes = 0;
+    hipEvent_t gev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     /* scan_select_topn: the compact key array (8 B per passing row), the
      * radix-select state block, and the refined mask / counts / bases — its
      * own buffers, the d_sel_* cache above is only ever read. Grow-only. */
@@ -3243,7 +3254,14 @@ void csgpu_release(cstripe_scan *s)
     if (g->d_tn_emit) HIP_DROP(hipFree(g->d_tn_emit));
     if (g->d_tn_out) HIP_DROP(hipFree(g->d_tn_out));
     if (g->d_tn_perm) HIP_DROP(hipFree(g->d_tn_perm));
+    if (g->d_gt_kept) HIP_DROP(hipFree(g->d_gt_kept));
+    if (g->d_gt_ord) HIP_DROP(hipFree(g->d_gt_ord));
+    if (g->d_gt_tie) HIP_DROP(hipFree(g->d_gt_tie));
+    if (g->d_gt_state) HIP_DROP(hipFree(g->d_gt_state));
+    if (g->d_gt_sel) HIP_DROP(hipFree(g->d_gt_sel));
+    if (g->d_gt_out) HIP_DROP(hipFree(g->d_gt_out));
     for (void *b : g->set_bufs) if (b) HIP_DROP(hipFree(b));
+    for (hipEvent_t e : g->gev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->tev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->hev) if (e) HIP_DROP(hipEventDestroy(e));
     for (hipEvent_t e : g->sev) if (e) HIP_DROP(hipEventDestroy(e));
@@ -6681,13 +6699,24 @@ static int hash_grow(T *&ptr, uint64_t &have, uint64_t need)
     return CSTRIPE_OK;
 }
 
-int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
-                     const uint32_t *key_cols, uint32_t n_key_cols,
-                     uint64_t capacity, cstripe_hgroups *out)
+/* what the front half shared by csgpu_agg_hashed and csgpu_agg_hashed_topn
+ * leaves behind: the key packing, and `n` compacted groups in d_hokeys /
+ * d_hocells */
+struct HashFront {
+    HashParams hp;
+    uint32_t kbits[CSTRIPE_MAX_HASH_KEY_COLS];
+    uint64_t n;
+};
+
+/* front half, host part: argument checks and key packing; no device work */
+static int hash_prepare(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                        const uint32_t *key_cols, uint32_t n_key_cols,
+                        uint64_t capacity, const cstripe_hgroups *out, HashFront &hf)
 {
-    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
-    cs_gpu_state *g = s->gpu;
     cstripe_reader *r = s->r;
+    hf = HashFront{};
+    HashParams &hp = hf.hp;
+    uint32_t *kbits = hf.kbits;
     if (!aggs || !out || !key_cols || n_aggs == 0) { cs_set_err("scan_agg_hashed: bad args"); return CSTRIPE_ERR_ARG; }
     if (n_aggs > MAX_AGGS) { cs_set_err("too many aggs"); return CSTRIPE_ERR_ARG; }
     if (s->preds.size() > MAX_PREDS) { cs_set_err("too many preds"); return CSTRIPE_ERR_ARG; }
@@ -6703,7 +6732,6 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
     }
     if (!out->partials) { cs_set_err("scan_agg_hashed: no partials destination"); return CSTRIPE_ERR_ARG; }
 
-    HashParams hp{};
     AggParams &p = hp.base;
     for (uint32_t i = 0; i < n_aggs; i++)
         if (aggs[i].kind > CSTRIPE_AGG_SUM_DISC_TAX_I64) { cs_set_err("agg %u: bad kind %u", i, aggs[i].kind); return CSTRIPE_ERR_ARG; }
@@ -6712,7 +6740,6 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
     /* key packing: [lo, hi] per key column from the SELECTED chunk groups'
      * skip nodes; total bits <= 63 keeps ~0ull free as the EMPTY marker */
     hp.n_key_cols = n_key_cols;
-    uint32_t kbits[CSTRIPE_MAX_HASH_KEY_COLS] = {0};
     bool ktext[CSTRIPE_MAX_HASH_KEY_COLS] = {false};
     uint32_t total_bits = 0;
     auto set_range = [&](uint32_t k, uint32_t col, bool full, int64_t tlo, int64_t thi) {
@@ -6798,12 +6825,23 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
                    "come from the selected chunk groups' min/max", total_bits, msg);
         return CSTRIPE_ERR_ARG;
     }
+    return CSTRIPE_OK;
+}
 
+/* front half, device part: decode, hash_init_kernel, hash_agg_kernel and
+ * hash_compact_kernel on the scan's stream, the count's copy-back, the
+ * device flags and the capacity check; hf.n = compacted groups (0 for an
+ * empty selection) */
+static int hash_execute(cstripe_scan *s, uint32_t n_aggs, uint64_t capacity, HashFront &hf)
+{
+    cs_gpu_state *g = s->gpu;
+    HashParams &hp = hf.hp;
+    const AggParams &p = hp.base;
+    hf.n = 0;
     hp.n_work = g->n_groups * p.tiles_per_group;
     if (hp.n_work == 0) {
         s->last_kernel_ms = s->last_decode_ms = s->last_agg_ms = 0;
         s->last_hash_init_ms = s->last_hash_scan_ms = s->last_hash_compact_ms = 0;
-        out->n_groups = 0;
         return CSTRIPE_OK;
     }
 
@@ -6908,7 +6946,22 @@ int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_a
                    h_n, (unsigned long long)capacity);
         return CSTRIPE_ERR_ARG;
     }
-    const uint64_t n = h_n;
+    hf.n = h_n;
+    return CSTRIPE_OK;
+}
+
+int csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                     const uint32_t *key_cols, uint32_t n_key_cols,
+                     uint64_t capacity, cstripe_hgroups *out)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    cs_gpu_state *g = s->gpu;
+    HashFront hf;
+    { int _rc = hash_prepare(s, aggs, n_aggs, key_cols, n_key_cols, capacity, out, hf); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_execute(s, n_aggs, capacity, hf); if (_rc != CSTRIPE_OK) return _rc; }
+    const HashParams &hp = hf.hp;
+    const uint32_t *kbits = hf.kbits;
+    const uint64_t n = hf.n;
     if (n == 0) { out->n_groups = 0; return CSTRIPE_OK; }
 
     std::vector<unsigned long long> h_keys(n);
@@ -7664,6 +7717,609 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
     s->last_topn_emit_ms = ms_e + ms_p;
     s->last_kernel_ms = ms_d + ms_d2 + ms_m + ms_o + ms_k + ms_s + ms_e + ms_p;
     out->n_rows = m;
+    return CSTRIPE_OK;
+}
+
+/* =====================================================================
+ * scan_agg_hashed_topn — GROUP BY ... [HAVING] ORDER BY ... LIMIT on the
+ * device: what WorkerLimitCount / WorkerSortClauseList and
+ * ProcessHavingClauseForWorkerQuery push to a worker whose groups are
+ * disjoint from every other shard's (multi_logical_optimizer.c:5039-5212,
+ * :2650-2682). Nothing new runs per row: after the front half of
+ * scan_agg_hashed the `n` compacted groups sit in d_hokeys / d_hocells, and
+ * on the scan's stream
+ *
+ *   gtopn_init_kernel     clears the state block
+ *   gtopn_range_kernel    per group: the HAVING atoms; kept groups append
+ *                         their index through one counter (wave-aggregated
+ *                         add, as hash_compact_kernel); per AGG order term
+ *                         the min / max order code over kept non-NULL groups
+ *                         (block reduction, one atomicMin / atomicMax per
+ *                         block); a flag per term for an integer sum outside
+ *                         int64. The state block's copy-back is the one sync
+ *                         before the selection; the host derives bits and
+ *                         shifts from it.
+ *   gtopn_key_kernel      per kept group the ORDER word (terms packed as
+ *                         topn_key_kernel packs columns: offset from lo,
+ *                         reversed for DESC, one NULL code at either end) and
+ *                         the TIE word (the key tuple re-packed in output
+ *                         order: column 0 most significant, NULL last)
+ *   radix select          topn_init / topn_hist / topn_pick, unchanged, over
+ *                         the order words: T1 and the number still wanted
+ *                         among the groups on T1; then gtopn_tieinit_kernel +
+ *                         gtopn_tiehist_kernel / topn_pick_kernel over the
+ *                         tie words of exactly those groups: T2. Tie words
+ *                         are distinct (one per key tuple), so
+ *                         ord < T1 | (ord == T1 & tie <= T2) holds for
+ *                         exactly `limit` groups. Skipped when kept <= limit.
+ *   gtopn_gather_kernel   the selected groups' packed key, order word, tie
+ *                         word and cells into limit-sized arrays
+ *   (host)                one DtoH copy, a sort by (order word, tie word),
+ *                         unpack, cell_to_partial
+ *
+ * No flag, fence, spin-wait or cross-block dependency exists inside a
+ * kernel; kernel boundaries order the stages. Words several blocks touch —
+ * the two counters, the range words, the overflow flags, the histogram bins —
+ * are updated by integer atomics (add / min / max / or) alone; the append
+ * positions the counters hand out depend on arrival order, the SET of
+ * appended groups and every value derived from it do not, and the host sort
+ * fixes the output order. Every loop is bounded by a count or a constant.
+ * ===================================================================== */
+
+#define GTOPN_GRID   1024
+#define GT_CNT  0u      /* COUNT kinds: the count, never NULL */
+#define GT_I64  1u      /* MIN / MAX_I64: the value in lo */
+#define GT_I128 2u      /* integer sums */
+#define GT_F64  3u
+
+struct GtopnParams {
+    uint32_t n_aggs, n_key_cols, n_having, n_order;
+    uint32_t hagg[CSTRIPE_MAX_HAVING], hop[CSTRIPE_MAX_HAVING], hcls[CSTRIPE_MAX_HAVING];
+    int64_t  hival[CSTRIPE_MAX_HAVING];
+    uint64_t hford[CSTRIPE_MAX_HAVING];                 /* topn_f64_ord(fval) */
+    uint32_t okind[CSTRIPE_MAX_GROUP_ORDER], oindex[CSTRIPE_MAX_GROUP_ORDER];
+    uint32_t oflags[CSTRIPE_MAX_GROUP_ORDER], ocls[CSTRIPE_MAX_GROUP_ORDER];
+    uint32_t oshift[CSTRIPE_MAX_GROUP_ORDER];
+    uint64_t olo[CSTRIPE_MAX_GROUP_ORDER], ospan[CSTRIPE_MAX_GROUP_ORDER];
+    uint32_t kshift[CSTRIPE_MAX_HASH_KEY_COLS], kbits[CSTRIPE_MAX_HASH_KEY_COLS];
+    uint32_t tshift[CSTRIPE_MAX_HASH_KEY_COLS];         /* tie word */
+    uint64_t kspan[CSTRIPE_MAX_HASH_KEY_COLS];
+};
+
+struct GtopnState {
+    unsigned long long n_kept;          /* groups HAVING kept */
+    unsigned long long n_out;           /* groups gathered */
+    unsigned long long lo[CSTRIPE_MAX_GROUP_ORDER];   /* order codes, AGG terms */
+    unsigned long long hi[CSTRIPE_MAX_GROUP_ORDER];
+    unsigned int ovf;                   /* bit t: term t met a sum outside int64 */
+    unsigned int pad;
+};
+
+static uint32_t gtopn_class(uint32_t kind)
+{
+    switch (kind) {
+        case CSTRIPE_AGG_COUNT_STAR: case CSTRIPE_AGG_COUNT_COL: return GT_CNT;
+        case CSTRIPE_AGG_MIN_I64: case CSTRIPE_AGG_MAX_I64: return GT_I64;
+        case CSTRIPE_AGG_SUM_F64: case CSTRIPE_AGG_MIN_F64: case CSTRIPE_AGG_MAX_F64: return GT_F64;
+        default: return GT_I128;
+    }
+}
+
+__host__ __device__ inline bool gtopn_null(const AccCell &c, uint32_t cls)
+{
+    return cls != GT_CNT && c.cnt == 0;
+}
+
+/* order code of a non-NULL aggregate value: signed integers flip the sign
+ * bit, floats go through topn_f64_ord; *ovf when an int128 sum is no int64 */
+__host__ __device__ inline uint64_t gtopn_ord(const AccCell &c, uint32_t cls, bool *ovf)
+{
+    *ovf = false;
+    if (cls == GT_CNT) return (uint64_t)c.cnt ^ TOPN_SIGN;
+    if (cls == GT_F64) return topn_f64_ord(c.f);
+    if (cls == GT_I128 && c.hi != (c.lo < 0 ? -1 : 0)) *ovf = true;
+    return (uint64_t)c.lo ^ TOPN_SIGN;
+}
+
+/* one HAVING atom on the aggregate's final value; a NULL aggregate fails */
+__device__ inline bool gtopn_having(const AccCell &c, uint32_t cls, uint32_t op,
+                                    int64_t ival, uint64_t ford)
+{
+    int cmp;
+    if (cls == GT_CNT) {
+        cmp = c.cnt < ival ? -1 : (c.cnt > ival ? 1 : 0);
+    } else {
+        if (c.cnt == 0) return false;
+        if (cls == GT_I64) {
+            cmp = c.lo < ival ? -1 : (c.lo > ival ? 1 : 0);
+        } else if (cls == GT_I128) {
+            /* the full int128 against the sign-extended constant */
+            const int64_t ihi = ival < 0 ? -1 : 0;
+            if (c.hi != ihi) cmp = c.hi < ihi ? -1 : 1;
+            else cmp = (uint64_t)c.lo < (uint64_t)ival ? -1
+                     : ((uint64_t)c.lo > (uint64_t)ival ? 1 : 0);
+        } else {
+            const uint64_t o = topn_f64_ord(c.f);
+            cmp = o < ford ? -1 : (o > ford ? 1 : 0);
+        }
+    }
+    switch (op) {
+        case CSTRIPE_PRED_LT: return cmp < 0;
+        case CSTRIPE_PRED_LE: return cmp <= 0;
+        case CSTRIPE_PRED_GT: return cmp > 0;
+        case CSTRIPE_PRED_GE: return cmp >= 0;
+        case CSTRIPE_PRED_EQ: return cmp == 0;
+        default:              return cmp != 0;
+    }
+}
+
+__device__ inline uint64_t gtopn_keycode(uint64_t key, const GtopnParams &gp, uint32_t k)
+{
+    return (key >> gp.kshift[k]) & ((1ull << gp.kbits[k]) - 1ull);   /* kbits <= 63 */
+}
+
+__global__ __launch_bounds__(WAVE) void gtopn_init_kernel(GtopnState *st)
+{
+    if (threadIdx.x == 0) { st->n_kept = 0; st->n_out = 0; st->ovf = 0; st->pad = 0; }
+    if (threadIdx.x < CSTRIPE_MAX_GROUP_ORDER) {
+        st->lo[threadIdx.x] = ~0ull;
+        st->hi[threadIdx.x] = 0;
+    }
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void gtopn_range_kernel(
+    const AccCell *__restrict__ cells, uint64_t n, uint32_t *__restrict__ kept,
+    GtopnState *st, const GtopnParams gp)
+{
+    __shared__ unsigned long long s_lo[CSTRIPE_MAX_GROUP_ORDER][AGG_BLOCK / WAVE];
+    __shared__ unsigned long long s_hi[CSTRIPE_MAX_GROUP_ORDER][AGG_BLOCK / WAVE];
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint32_t wid = threadIdx.x / WAVE;
+    unsigned long long lo[CSTRIPE_MAX_GROUP_ORDER], hi[CSTRIPE_MAX_GROUP_ORDER];
+    #pragma unroll
+    for (uint32_t t = 0; t < CSTRIPE_MAX_GROUP_ORDER; t++) { lo[t] = ~0ull; hi[t] = 0; }
+    unsigned int ovf = 0;
+    /* wave-uniform trip count: the ballot below needs every lane present */
+    for (uint64_t base = (uint64_t)blockIdx.x * AGG_BLOCK; base < n;
+         base += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const uint64_t i = base + threadIdx.x;
+        bool keep = i < n;
+        if (keep)
+            for (uint32_t h = 0; h < gp.n_having; h++)
+                keep = keep && gtopn_having(cells[i * gp.n_aggs + gp.hagg[h]], gp.hcls[h],
+                                            gp.hop[h], gp.hival[h], gp.hford[h]);
+        const uint64_t m = __ballot(keep);
+        if (m == 0) continue;
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        unsigned long long wbase = 0;
+        if ((int)lane == leader)
+            wbase = atomicAdd(&st->n_kept, (unsigned long long)__popcll(m));
+        wbase = (unsigned long long)__shfl((long long)wbase, leader, WAVE);
+        if (!keep) continue;
+        /* every group is counted once, so the index stays below n */
+        const uint64_t at = wbase + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (at < n) kept[at] = (uint32_t)i;
+        #pragma unroll
+        for (uint32_t t = 0; t < CSTRIPE_MAX_GROUP_ORDER; t++) {
+            if (t >= gp.n_order || gp.okind[t] != CSTRIPE_GORDER_AGG) continue;
+            const AccCell c = cells[i * gp.n_aggs + gp.oindex[t]];
+            if (gtopn_null(c, gp.ocls[t])) continue;
+            bool of;
+            const unsigned long long o = gtopn_ord(c, gp.ocls[t], &of);
+            if (of) { ovf |= 1u << t; continue; }
+            lo[t] = o < lo[t] ? o : lo[t];
+            hi[t] = o > hi[t] ? o : hi[t];
+        }
+    }
+    if (ovf) atomicOr(&st->ovf, ovf);
+    #pragma unroll
+    for (uint32_t t = 0; t < CSTRIPE_MAX_GROUP_ORDER; t++) {
+        unsigned long long l = lo[t], h = hi[t];
+        #pragma unroll
+        for (int d = WAVE / 2; d > 0; d >>= 1) {
+            const unsigned long long l2 = (unsigned long long)__shfl_xor((long long)l, d, WAVE);
+            const unsigned long long h2 = (unsigned long long)__shfl_xor((long long)h, d, WAVE);
+            l = l2 < l ? l2 : l;
+            h = h2 > h ? h2 : h;
+        }
+        if (lane == 0) { s_lo[t][wid] = l; s_hi[t][wid] = h; }
+    }
+    __syncthreads();
+    if (threadIdx.x < CSTRIPE_MAX_GROUP_ORDER) {
+        const uint32_t t = threadIdx.x;
+        unsigned long long l = ~0ull, h = 0;
+        for (uint32_t w = 0; w < AGG_BLOCK / WAVE; w++) {
+            l = s_lo[t][w] < l ? s_lo[t][w] : l;
+            h = s_hi[t][w] > h ? s_hi[t][w] : h;
+        }
+        if (l <= h) {                   /* this block saw a value of term t */
+            atomicMin(&st->lo[t], l);
+            atomicMax(&st->hi[t], h);
+        }
+    }
+}
+
+__global__ __launch_bounds__(AGG_BLOCK) void gtopn_key_kernel(
+    const unsigned long long *__restrict__ okeys, const AccCell *__restrict__ cells,
+    const uint32_t *__restrict__ kept, uint64_t n_kept, uint64_t *__restrict__ ord,
+    uint64_t *__restrict__ tie, const GtopnParams gp)
+{
+    for (uint64_t j = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; j < n_kept;
+         j += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const uint64_t i = kept[j];
+        const uint64_t key = okeys[i];
+        uint64_t ow = 0;
+        for (uint32_t t = 0; t < gp.n_order; t++) {
+            const uint32_t fl = gp.oflags[t];
+            const uint64_t span = gp.ospan[t];
+            bool null;
+            uint64_t d = 0;
+            if (gp.okind[t] == CSTRIPE_GORDER_AGG) {
+                const AccCell c = cells[i * gp.n_aggs + gp.oindex[t]];
+                null = gtopn_null(c, gp.ocls[t]);
+                if (!null) {
+                    bool of;
+                    d = gtopn_ord(c, gp.ocls[t], &of) - gp.olo[t];
+                    if (d > span) d = span;     /* measured over these groups: never */
+                }
+            } else {
+                const uint64_t kc = gtopn_keycode(key, gp, gp.oindex[t]);
+                null = kc == 0;
+                d = kc - 1;
+            }
+            uint64_t code;
+            if (!null) {
+                if (fl & CSTRIPE_ORDER_DESC) d = span - d;
+                code = (fl & CSTRIPE_ORDER_NULLS_FIRST) ? d + 1 : d;
+            } else {
+                code = (fl & CSTRIPE_ORDER_NULLS_FIRST) ? 0 : span + 1;
+            }
+            ow |= code << gp.oshift[t];
+        }
+        uint64_t tw = 0;
+        for (uint32_t k = 0; k < gp.n_key_cols; k++) {
+            const uint64_t kc = gtopn_keycode(key, gp, k);
+            tw |= (kc == 0 ? gp.kspan[k] + 1 : kc - 1) << gp.tshift[k];
+        }
+        ord[j] = ow;
+        tie[j] = tw;
+    }
+}
+
+/* the tie-word select starts where the order-word select ended: it wants
+ * the st_ord->k smallest tie words among the groups on the threshold */
+__global__ __launch_bounds__(AGG_BLOCK) void gtopn_tieinit_kernel(
+    TopnState *st_tie, const TopnState *__restrict__ st_ord)
+{
+    st_tie->hist[threadIdx.x] = 0;      /* AGG_BLOCK == 256 bins */
+    if (threadIdx.x == 0) { st_tie->prefix = 0; st_tie->k = st_ord->k; }
+}
+
+/* topn_hist_kernel over the tie words, restricted to the groups whose order
+ * word equals the threshold */
+__global__ __launch_bounds__(AGG_BLOCK) void gtopn_tiehist_kernel(
+    const uint64_t *__restrict__ ord, const uint64_t *__restrict__ tie, uint64_t n,
+    const TopnState *__restrict__ st_ord, TopnState *st_tie, uint32_t shift)
+{
+    __shared__ uint32_t lh[256];
+    lh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t T1 = st_ord->prefix;
+    const uint64_t prefix = st_tie->prefix;
+    const bool top = shift + 8 >= 64;
+    const uint32_t hs = top ? 0 : shift + 8;
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_BLOCK + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * AGG_BLOCK) {
+        if (ord[i] != T1) continue;
+        const uint64_t key = tie[i];
+        if (top || (key >> hs) == prefix)
+            atomicAdd(&lh[(key >> shift) & 0xFFu], 1u);
+    }
+    __syncthreads();
+    const uint32_t c = lh[threadIdx.x];
+    if (c) atomicAdd(&st_tie->hist[threadIdx.x], (unsigned long long)c);
+}
+
+/* out: [m] packed keys | [m] order words | [m] tie words | [m * n_aggs] cells */
+__global__ __launch_bounds__(AGG_BLOCK) void gtopn_gather_kernel(
+    const unsigned long long *__restrict__ okeys, const AccCell *__restrict__ cells,
+    const uint32_t *__restrict__ kept, uint64_t n_kept,
+    const uint64_t *__restrict__ ord, const uint64_t *__restrict__ tie,
+    const TopnState *__restrict__ st_ord, const TopnState *__restrict__ st_tie,
+    int all, GtopnState *st, uint64_t m, uint8_t *__restrict__ outb, uint32_t n_aggs)
+{
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint64_t T1 = all ? 0 : st_ord->prefix;
+    const uint64_t T2 = all ? 0 : st_tie->prefix;
+    uint64_t *o_key = (uint64_t *)outb;
+    uint64_t *o_ord = o_key + m;
+    uint64_t *o_tie = o_ord + m;
+    AccCell *o_cells = (AccCell *)(o_tie + m);
+    /* wave-uniform trip count: the ballot below needs every lane present */
+    for (uint64_t base = (uint64_t)blockIdx.x * AGG_BLOCK; base < n_kept;
+         base += (uint64_t)gridDim.x * AGG_BLOCK) {
+        const uint64_t j = base + threadIdx.x;
+        bool take = false;
+        uint64_t ow = 0, tw = 0;
+        if (j < n_kept) {
+            ow = ord[j];
+            tw = tie[j];
+            take = all || ow < T1 || (ow == T1 && tw <= T2);
+        }
+        const uint64_t mk = __ballot(take);
+        if (mk == 0) continue;
+        const int leader = __ffsll((unsigned long long)mk) - 1;
+        unsigned long long wbase = 0;
+        if ((int)lane == leader)
+            wbase = atomicAdd(&st->n_out, (unsigned long long)__popcll(mk));
+        wbase = (unsigned long long)__shfl((long long)wbase, leader, WAVE);
+        if (!take) continue;
+        /* the count stays exact (the host checks it); writes are bounded */
+        const uint64_t at = wbase + (uint64_t)__popcll(mk & ((1ull << lane) - 1ull));
+        if (at >= m) continue;
+        const uint64_t i = kept[j];
+        o_key[at] = okeys[i];
+        o_ord[at] = ow;
+        o_tie[at] = tw;
+        for (uint32_t a = 0; a < n_aggs; a++)
+            o_cells[at * n_aggs + a] = cells[i * n_aggs + a];
+    }
+}
+
+int csgpu_agg_hashed_topn(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                          const uint32_t *key_cols, uint32_t n_key_cols,
+                          uint64_t capacity, const cstripe_having *having,
+                          uint32_t n_having, const cstripe_group_order *order,
+                          uint32_t n_order, uint64_t limit, cstripe_hgroups *out)
+{
+    if (!s->gpu) { cs_set_err("scan not staged — call cstripe_gpu_stage first (GPU required; no CPU fallback)"); return CSTRIPE_ERR_NOGPU; }
+    cs_gpu_state *g = s->gpu;
+    if (limit == 0 || limit > CSTRIPE_MAX_TOPN) {
+        cs_set_err("scan_agg_hashed_topn: limit %llu outside 1..%u",
+                   (unsigned long long)limit, CSTRIPE_MAX_TOPN);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (n_order > CSTRIPE_MAX_GROUP_ORDER || (n_order && !order)) {
+        cs_set_err("scan_agg_hashed_topn: %u order terms (0..%d)", n_order, CSTRIPE_MAX_GROUP_ORDER);
+        return CSTRIPE_ERR_ARG;
+    }
+    if (n_having > CSTRIPE_MAX_HAVING || (n_having && !having)) {
+        cs_set_err("scan_agg_hashed_topn: %u HAVING atoms (0..%d)", n_having, CSTRIPE_MAX_HAVING);
+        return CSTRIPE_ERR_ARG;
+    }
+    HashFront hf;
+    { int _rc = hash_prepare(s, aggs, n_aggs, key_cols, n_key_cols, capacity, out, hf); if (_rc != CSTRIPE_OK) return _rc; }
+    const HashParams &hp = hf.hp;
+
+    GtopnParams gp{};
+    gp.n_aggs = n_aggs;
+    gp.n_key_cols = n_key_cols;
+    gp.n_having = n_having;
+    gp.n_order = n_order;
+    for (uint32_t h = 0; h < n_having; h++) {
+        if (having[h].agg >= n_aggs) {
+            cs_set_err("scan_agg_hashed_topn: HAVING atom %u: agg %u out of range (%u aggs)",
+                       h, having[h].agg, n_aggs);
+            return CSTRIPE_ERR_ARG;
+        }
+        if (having[h].op > CSTRIPE_PRED_NE) {
+            cs_set_err("scan_agg_hashed_topn: HAVING atom %u: bad op %u (LT..NE)", h, having[h].op);
+            return CSTRIPE_ERR_ARG;
+        }
+        gp.hagg[h] = having[h].agg;
+        gp.hop[h] = having[h].op;
+        gp.hcls[h] = gtopn_class(aggs[having[h].agg].kind);
+        gp.hival[h] = having[h].ival;
+        gp.hford[h] = topn_f64_ord(having[h].fval);
+    }
+    for (uint32_t t = 0; t < n_order; t++) {
+        const cstripe_group_order &o = order[t];
+        if (o.kind > CSTRIPE_GORDER_KEY) {
+            cs_set_err("scan_agg_hashed_topn: order term %u: bad kind %u", t, o.kind);
+            return CSTRIPE_ERR_ARG;
+        }
+        const bool is_key = o.kind == CSTRIPE_GORDER_KEY;
+        if (o.index >= (is_key ? n_key_cols : n_aggs)) {
+            cs_set_err("scan_agg_hashed_topn: order term %u: %s index %u out of range", t,
+                       is_key ? "key" : "agg", o.index);
+            return CSTRIPE_ERR_ARG;
+        }
+        if (o.flags & ~(CSTRIPE_ORDER_DESC | CSTRIPE_ORDER_NULLS_FIRST)) {
+            cs_set_err("scan_agg_hashed_topn: order term %u: unknown flags 0x%x", t, o.flags);
+            return CSTRIPE_ERR_ARG;
+        }
+        for (uint32_t j = 0; j < t; j++)
+            if (order[j].kind == o.kind && order[j].index == o.index) {
+                cs_set_err("scan_agg_hashed_topn: order term %u repeats term %u", t, j);
+                return CSTRIPE_ERR_ARG;
+            }
+        if (is_key && cs_col_type(s, key_cols[o.index]) == CSTRIPE_TEXT) {
+            cs_set_err("scan_select_topn: order col %u is TEXT — its row-level order in this "
+                       "ABI is whole-slot, not collation; order by a VARTEXT column instead",
+                       key_cols[o.index]);
+            return CSTRIPE_ERR_ARG;
+        }
+        gp.okind[t] = o.kind;
+        gp.oindex[t] = o.index;
+        gp.oflags[t] = o.flags;
+        gp.ocls[t] = is_key ? 0 : gtopn_class(aggs[o.index].kind);
+    }
+    uint32_t tie_bits = 0;
+    for (uint32_t k = 0; k < n_key_cols; k++) {
+        if (hp.klex[k]) {
+            cs_set_err("scan_agg_hashed_topn: the key tuple only packs through the TEXT "
+                       "order-key fallback, whose packed order is not the output order — "
+                       "use cstripe_scan_agg_hashed");
+            return CSTRIPE_ERR_ARG;
+        }
+        gp.kshift[k] = hp.kshift[k];
+        gp.kbits[k] = hf.kbits[k];
+        gp.kspan[k] = hp.kspan[k];
+        tie_bits += hf.kbits[k];
+    }
+    /* tie word: column 0 most significant; same widths, so <= 63 bits */
+    for (uint32_t k = 0, sh = tie_bits; k < n_key_cols; k++) {
+        sh -= hf.kbits[k];
+        gp.tshift[k] = sh;
+    }
+
+    s->last_gt_groups = s->last_gt_kept = 0;
+    s->last_gt_range_ms = s->last_gt_select_ms = s->last_gt_emit_ms = 0;
+    { int _rc = hash_execute(s, n_aggs, capacity, hf); if (_rc != CSTRIPE_OK) return _rc; }
+    const uint64_t n = hf.n;
+    s->last_gt_groups = n;
+    if (n == 0) { out->n_groups = 0; return CSTRIPE_OK; }
+
+    for (hipEvent_t &e : g->gev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    { int _rc = hash_grow(g->d_gt_kept, g->gt_kept_n, capacity); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_gt_ord, g->gt_ord_n, capacity); if (_rc != CSTRIPE_OK) return _rc; }
+    { int _rc = hash_grow(g->d_gt_tie, g->gt_tie_n, capacity); if (_rc != CSTRIPE_OK) return _rc; }
+    if (!g->d_gt_state) HIP_TRY(hipMalloc(&g->d_gt_state, sizeof(GtopnState)));
+    if (!g->d_gt_sel) HIP_TRY(hipMalloc(&g->d_gt_sel, 2 * sizeof(TopnState)));
+
+    const uint32_t ngrid = (uint32_t)std::min<uint64_t>((n + AGG_BLOCK - 1) / AGG_BLOCK, GTOPN_GRID);
+    HIP_TRY(hipEventRecord(g->gev[0], g->stream));
+    hipLaunchKernelGGL(gtopn_init_kernel, dim3(1), dim3(WAVE), 0, g->stream, g->d_gt_state);
+    hipLaunchKernelGGL(gtopn_range_kernel, dim3(ngrid), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_hocells, n, g->d_gt_kept, g->d_gt_state, gp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->gev[1], g->stream));
+
+    /* the state block: the single sync before the selection */
+    GtopnState h_st{};
+    HIP_TRY(hipMemcpyAsync(&h_st, g->d_gt_state, sizeof(h_st), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    float ms_r = 0;
+    (void)hipEventElapsedTime(&ms_r, g->gev[0], g->gev[1]);
+    s->last_gt_range_ms = ms_r;
+    s->last_kernel_ms += ms_r;
+    const uint64_t n_kept = h_st.n_kept;
+    s->last_gt_kept = n_kept;
+    if (n_kept > n) {
+        cs_set_err("scan_agg_hashed_topn: HAVING kept %llu of %llu groups",
+                   (unsigned long long)n_kept, (unsigned long long)n);
+        return CSTRIPE_ERR;
+    }
+    for (uint32_t t = 0; t < n_order; t++)
+        if (h_st.ovf & (1u << t)) {
+            cs_set_err("scan_agg_hashed_topn: order term %u: agg %u (kind %u) has a sum outside "
+                       "int64 in a surviving group — such a value does not fit the 64-bit order "
+                       "word", t, gp.oindex[t], aggs[gp.oindex[t]].kind);
+            return CSTRIPE_ERR_ARG;
+        }
+    if (n_kept == 0) { out->n_groups = 0; return CSTRIPE_OK; }
+
+    /* bits and shifts of the order word, term 0 most significant */
+    uint32_t obits[CSTRIPE_MAX_GROUP_ORDER] = {0};
+    uint32_t order_bits = 0;
+    for (uint32_t t = 0; t < n_order; t++) {
+        if (gp.okind[t] == CSTRIPE_GORDER_AGG) {
+            const bool any = h_st.lo[t] <= h_st.hi[t];      /* a non-NULL value */
+            gp.olo[t] = any ? h_st.lo[t] : 0;
+            gp.ospan[t] = any ? h_st.hi[t] - h_st.lo[t] : 0;
+        } else {
+            gp.olo[t] = 0;
+            gp.ospan[t] = hp.kspan[gp.oindex[t]];
+        }
+        obits[t] = gp.ospan[t] == ~0ull ? 65u : hash_bitlen(gp.ospan[t] + 1);
+        order_bits += obits[t];
+    }
+    if (order_bits > 64) {
+        char msg[200];
+        int w = 0;
+        for (uint32_t t = 0; t < n_order; t++)
+            w += snprintf(msg + w, sizeof(msg) - (size_t)w, "%sterm %u (%s %u): %u bits",
+                          t ? ", " : "", t,
+                          gp.okind[t] == CSTRIPE_GORDER_KEY ? "key" : "agg", gp.oindex[t], obits[t]);
+        cs_set_err("scan_agg_hashed_topn: order word needs %u bits > 64 (%s) — an aggregate "
+                   "term's range is measured over the surviving groups, a key term's comes "
+                   "from the key packing", order_bits, msg);
+        return CSTRIPE_ERR_ARG;
+    }
+    for (uint32_t t = 0, sh = order_bits; t < n_order; t++) {
+        sh -= obits[t];
+        gp.oshift[t] = sh;
+    }
+
+    const uint64_t m = std::min<uint64_t>(limit, n_kept);
+    const bool selecting = n_kept > limit;
+    const uint64_t out_bytes = m * (3 * sizeof(uint64_t) + (uint64_t)n_aggs * sizeof(AccCell));
+    { int _rc = hash_grow(g->d_gt_out, g->gt_out_bytes, out_bytes); if (_rc != CSTRIPE_OK) return _rc; }
+    TopnState *st_ord = g->d_gt_sel, *st_tie = g->d_gt_sel + 1;
+    const uint32_t kgrid = (uint32_t)std::min<uint64_t>((n_kept + AGG_BLOCK - 1) / AGG_BLOCK, GTOPN_GRID);
+
+    HIP_TRY(hipEventRecord(g->gev[2], g->stream));
+    hipLaunchKernelGGL(gtopn_key_kernel, dim3(kgrid), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_hokeys, g->d_hocells, g->d_gt_kept, n_kept,
+                       g->d_gt_ord, g->d_gt_tie, gp);
+    HIP_TRY(hipGetLastError());
+    if (selecting) {
+        const uint32_t orounds = (order_bits + 7) / 8;      /* 0..8 */
+        const uint32_t trounds = (tie_bits + 7) / 8;        /* 1..8 */
+        hipLaunchKernelGGL(topn_init_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                           st_ord, limit);
+        for (uint32_t rd = 0; rd < orounds; rd++) {
+            const uint32_t shift = 8 * (orounds - 1 - rd);
+            hipLaunchKernelGGL(topn_hist_kernel, dim3(kgrid), dim3(AGG_BLOCK), 0, g->stream,
+                               g->d_gt_ord, n_kept, st_ord, shift);
+            hipLaunchKernelGGL(topn_pick_kernel, dim3(1), dim3(WAVE), 0, g->stream, st_ord);
+        }
+        hipLaunchKernelGGL(gtopn_tieinit_kernel, dim3(1), dim3(AGG_BLOCK), 0, g->stream,
+                           st_tie, st_ord);
+        for (uint32_t rd = 0; rd < trounds; rd++) {
+            const uint32_t shift = 8 * (trounds - 1 - rd);
+            hipLaunchKernelGGL(gtopn_tiehist_kernel, dim3(kgrid), dim3(AGG_BLOCK), 0, g->stream,
+                               g->d_gt_ord, g->d_gt_tie, n_kept, st_ord, st_tie, shift);
+            hipLaunchKernelGGL(topn_pick_kernel, dim3(1), dim3(WAVE), 0, g->stream, st_tie);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(g->gev[3], g->stream));
+    hipLaunchKernelGGL(gtopn_gather_kernel, dim3(kgrid), dim3(AGG_BLOCK), 0, g->stream,
+                       g->d_hokeys, g->d_hocells, g->d_gt_kept, n_kept, g->d_gt_ord,
+                       g->d_gt_tie, st_ord, st_tie, selecting ? 0 : 1, g->d_gt_state, m,
+                       g->d_gt_out, n_aggs);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->gev[4], g->stream));
+
+    /* limit-sized: the one result copy */
+    std::vector<uint64_t> h_out(out_bytes / sizeof(uint64_t));
+    HIP_TRY(hipMemcpyAsync(&h_st, g->d_gt_state, sizeof(h_st), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(h_out.data(), g->d_gt_out, out_bytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    float ms_s = 0, ms_e = 0;
+    (void)hipEventElapsedTime(&ms_s, g->gev[2], g->gev[3]);
+    (void)hipEventElapsedTime(&ms_e, g->gev[3], g->gev[4]);
+    s->last_gt_select_ms = ms_s;
+    s->last_gt_emit_ms = ms_e;
+    s->last_kernel_ms += ms_s + ms_e;
+    if (h_st.n_out != m) {
+        cs_set_err("scan_agg_hashed_topn: selection kept %llu groups, expected %llu",
+                   (unsigned long long)h_st.n_out, (unsigned long long)m);
+        return CSTRIPE_ERR;
+    }
+
+    const uint64_t *h_key = h_out.data(), *h_ord = h_key + m, *h_tie = h_ord + m;
+    const AccCell *h_cells = (const AccCell *)(h_tie + m);
+    std::vector<uint32_t> perm(m);
+    for (uint64_t i = 0; i < m; i++) perm[i] = (uint32_t)i;
+    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
+        if (h_ord[a] != h_ord[b]) return h_ord[a] < h_ord[b];
+        return h_tie[a] < h_tie[b];
+    });
+    for (uint64_t oi = 0; oi < m; oi++) {
+        const uint64_t i = perm[oi];
+        for (uint32_t k = 0; k < n_key_cols; k++) {
+            const uint64_t code = (h_key[i] >> hp.kshift[k]) & ((1ull << hf.kbits[k]) - 1ull);
+            out->key_nulls[k][oi] = code == 0 ? 1 : 0;
+            out->keys[k][oi] = code == 0 ? 0 : (int64_t)((uint64_t)hp.klo[k] + (code - 1));
+        }
+        for (uint32_t a = 0; a < n_aggs; a++)
+            out->partials[(size_t)oi * n_aggs + a] =
+                cell_to_partial(aggs[a].kind, h_cells[(size_t)i * n_aggs + a]);
+    }
+    out->n_groups = m;
     return CSTRIPE_OK;
 }
 

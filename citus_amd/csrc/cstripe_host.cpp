@@ -1970,6 +1970,32 @@ extern "C" int cstripe_scan_last_hash_ms(const cstripe_scan *s, double *init_ms,
     return CSTRIPE_OK;
 }
 
+extern "C" int cstripe_scan_agg_hashed_topn(cstripe_scan *s,
+        const cstripe_agg_spec *aggs, uint32_t n_aggs,
+        const uint32_t *key_cols, uint32_t n_key_cols, uint64_t capacity,
+        const cstripe_having *having, uint32_t n_having,
+        const cstripe_group_order *order, uint32_t n_order,
+        uint64_t limit, cstripe_hgroups *out)
+{
+    if (!s) { cs_set_err("scan_agg_hashed_topn: bad args"); return CSTRIPE_ERR_ARG; }
+    /* the staged check comes first; argument checks follow it there */
+    return csgpu_agg_hashed_topn(s, aggs, n_aggs, key_cols, n_key_cols, capacity,
+                                 having, n_having, order, n_order, limit, out);
+}
+
+extern "C" int cstripe_scan_last_group_topn(const cstripe_scan *s, uint64_t *n_groups,
+                                            uint64_t *n_kept, double *range_ms,
+                                            double *select_ms, double *emit_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (n_groups) *n_groups = s->last_gt_groups;
+    if (n_kept) *n_kept = s->last_gt_kept;
+    if (range_ms) *range_ms = s->last_gt_range_ms;
+    if (select_ms) *select_ms = s->last_gt_select_ms;
+    if (emit_ms) *emit_ms = s->last_gt_emit_ms;
+    return CSTRIPE_OK;
+}
+
 /* ============================ combine ============================ */
 
 static bool agg_is_count(uint32_t k)

@@ -136,6 +136,11 @@ struct cstripe_scan {
     double last_topn_key_ms = 0.0;        /* scan_select_topn per-stage split */
     double last_topn_select_ms = 0.0;
     double last_topn_emit_ms = 0.0;
+    uint64_t last_gt_groups = 0;          /* scan_agg_hashed_topn: groups, kept */
+    uint64_t last_gt_kept = 0;
+    double last_gt_range_ms = 0.0;        /* and its per-stage split */
+    double last_gt_select_ms = 0.0;
+    double last_gt_emit_ms = 0.0;
     /* random-access read cache (the reference keeps the current stripe
      * open across ColumnarReadRowByRowNumber calls the same way) */
     int64_t rr_gi = -1;
@@ -201,6 +206,14 @@ int  csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
 int  csgpu_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
                       const uint32_t *key_cols, uint32_t n_key_cols,
                       uint64_t capacity, cstripe_hgroups *out);
+/* GROUP BY ... HAVING ... ORDER BY ... LIMIT: the front half of
+ * csgpu_agg_hashed, then range / HAVING -> keys -> radix select -> gather
+ * over the compacted group table; only `limit` groups are copied back */
+int  csgpu_agg_hashed_topn(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n_aggs,
+                           const uint32_t *key_cols, uint32_t n_key_cols,
+                           uint64_t capacity, const cstripe_having *having,
+                           uint32_t n_having, const cstripe_group_order *order,
+                           uint32_t n_order, uint64_t limit, cstripe_hgroups *out);
 /* ORDER BY ... LIMIT (key build -> radix select -> refine -> emit ->
  * permute); reads the select cache, writes only its own buffers */
 int  csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order,

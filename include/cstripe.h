@@ -852,6 +852,110 @@ int cstripe_scan_agg_hashed(cstripe_scan *s, const cstripe_agg_spec *aggs, uint3
                             uint64_t capacity, cstripe_hgroups *out);
 int cstripe_scan_last_hash_ms(const cstripe_scan *s, double *init_ms, double *scan_ms, double *compact_ms);
 
+/* ---- GROUP BY ... [HAVING] ORDER BY ... LIMIT (device top-N over groups) ----
+ * The last step of the reference's pushed-down grouped plan. WorkerLimitCount
+ * (multi_logical_optimizer.c:5039-5140) hands each shard the exact LIMIT
+ * limit+offset with the ORDER BY when the GROUP BY holds the partition column
+ * (groupedByDisjointPartitionColumn, :5081-5085 — every group lives on one
+ * shard), and an approximate row count when the ORDER BY names a commutative
+ * aggregate (:5094-5111); WorkerSortClauseList (:5163-5212) supplies the
+ * order, and HAVING goes to the worker in the same disjoint case
+ * (ProcessHavingClauseForWorkerQuery, :2650-2682). Here the group table of
+ * cstripe_scan_agg_hashed stays in HBM, a set of kernels filters, ranks and
+ * selects over it, and only `limit` groups are copied back. */
+#define CSTRIPE_MAX_GROUP_ORDER 4
+#define CSTRIPE_MAX_HAVING      4
+#define CSTRIPE_GORDER_AGG 0u      /* index = position in aggs[]     */
+#define CSTRIPE_GORDER_KEY 1u      /* index = position in key_cols[] */
+typedef struct cstripe_group_order {
+    uint32_t kind;     /* CSTRIPE_GORDER_* */
+    uint32_t index;
+    uint32_t flags;    /* CSTRIPE_ORDER_DESC | CSTRIPE_ORDER_NULLS_FIRST, taken
+                        * literally as in cstripe_scan_select_topn */
+    uint32_t _pad;
+} cstripe_group_order;
+typedef struct cstripe_having {
+    uint32_t agg;      /* position in aggs[] */
+    uint32_t op;       /* CSTRIPE_PRED_LT .. CSTRIPE_PRED_NE; atoms are ANDed */
+    int64_t  ival;     /* constant for COUNT and integer kinds */
+    double   fval;     /* constant for f64 kinds */
+} cstripe_having;
+
+/* cstripe_scan_agg_hashed_topn:
+ *  - Groups, aggregates, filter, NULL keys: exactly cstripe_scan_agg_hashed —
+ *    the same key types, packing, 63-bit rule, `capacity` / slots and error
+ *    messages (they keep the scan_agg_hashed prefix: one front half serves
+ *    both calls); CSTRIPE_HASH_LDS_SLOTS is honoured; lookup-derived and
+ *    VARTEXT key columns are accepted. `capacity` bounds the number of groups
+ *    BEFORE HAVING. Every destination in `out` holds `limit` entries.
+ *  - HAVING: a group survives iff every atom is true on the aggregate's final
+ *    value. COUNT kinds compare the count with ival; integer kinds compare
+ *    the full int128 with ival, exactly (a sum beyond 64 bits still compares
+ *    correctly); f64 kinds compare with fval in PG float order (NaN greatest
+ *    and equal to itself, -0.0 = +0.0). A NULL aggregate (no contributing
+ *    row) fails its atom. n_having == 0 keeps every group.
+ *  - Order: lexicographic over order[0..n_order). An AGG term orders by the
+ *    aggregate's value — signed for COUNT and integer kinds, PG float order
+ *    for f64 kinds; a NULL aggregate sorts after every value, or before with
+ *    CSTRIPE_ORDER_NULLS_FIRST. A KEY term orders by that key column's value
+ *    as cstripe_scan_select_topn orders the column (VARTEXT by rank, a NULL
+ *    key last or first by the flag). Groups equal on every term come out
+ *    ascending by key tuple exactly as cstripe_scan_agg_hashed sorts them
+ *    (column 0 most significant, signed, NULL last, TEXT by slot value). The
+ *    result is a total order, independent of the table's slot order and
+ *    identical on every call; n_order == 0 is legal and means "the first
+ *    `limit` surviving groups in key order". One stated exception: a SUM_F64
+ *    term is only as reproducible as the atomic f64 sum itself.
+ *  - Result: out->n_groups = min(limit, surviving groups), in the requested
+ *    order; keys, key_nulls and partials converted exactly as
+ *    cstripe_scan_agg_hashed converts them.
+ *  - Supported domain: the ORDER terms pack into ONE 64-bit order word, term
+ *    0 most significant. An AGG term's [lo, hi] is measured on the device
+ *    over the surviving non-NULL groups and needs bitlen(hi - lo + 1) bits —
+ *    the value offsets plus one NULL code at either end; a KEY term uses the
+ *    range the key packing derived. (An f64 term is measured in order codes
+ *    of the bit pattern: values of one sign and similar magnitude take few
+ *    bits, values of both signs take all 64, leaving room for no other
+ *    term.) More than 64 bits is CSTRIPE_ERR_ARG, the
+ *    message naming each term's bits. An integer AGG order term whose value
+ *    in some surviving group does not fit int64 is CSTRIPE_ERR_ARG naming the
+ *    aggregate (HAVING has no such limit). The tie word is the key tuple
+ *    re-packed in output order, at most 63 bits.
+ *  - Errors: an unstaged scan returns CSTRIPE_ERR_NOGPU, checked first.
+ *    CSTRIPE_ERR_ARG: limit 0 or above CSTRIPE_MAX_TOPN; n_order above
+ *    CSTRIPE_MAX_GROUP_ORDER or n_having above CSTRIPE_MAX_HAVING; a bad
+ *    kind, index, op or flags; a repeated order term; a TEXT key column named
+ *    as a KEY order term (the message of cstripe_scan_select_topn); a key
+ *    tuple that only packs through the TEXT order-key fallback (use
+ *    cstripe_scan_agg_hashed); everything cstripe_scan_agg_hashed rejects.
+ *    Zero selected chunk groups, zero passing rows or zero surviving groups:
+ *    CSTRIPE_OK, n_groups = 0.
+ *  - Device work after the shared front half (table init, scan + hash
+ *    aggregate, compaction): a range / HAVING kernel (kept indices, per-term
+ *    min / max, the out-of-int64 flag; its small state block is the one
+ *    copy-back before the selection), a key kernel (order word + tie word per
+ *    kept group), the 8-bit radix select of cstripe_scan_select_topn over the
+ *    order word and then over the tie word among the groups on the threshold
+ *    (skipped when kept <= limit), and a gather of the selected groups. One
+ *    DtoH copy of limit * (24 + 32 * n_aggs) bytes follows; the host sorts
+ *    those by (order word, tie word).
+ *  - Re-invocable, and may be interleaved with every other scan call without
+ *    changing any of their results: its buffers are its own or the ones
+ *    cstripe_scan_agg_hashed re-initialises per call.
+ *    cstripe_scan_last_hash_ms reports the front half of this call;
+ *    cstripe_scan_last_group_topn the groups before and after HAVING and the
+ *    device time of the range / HAVING kernel, the key build plus selection,
+ *    and the gather (all 0 when no group was found). Any out pointer may be
+ *    NULL. */
+int cstripe_scan_agg_hashed_topn(cstripe_scan *s,
+        const cstripe_agg_spec *aggs, uint32_t n_aggs,
+        const uint32_t *key_cols, uint32_t n_key_cols, uint64_t capacity,
+        const cstripe_having *having, uint32_t n_having,
+        const cstripe_group_order *order, uint32_t n_order,
+        uint64_t limit, cstripe_hgroups *out);
+int cstripe_scan_last_group_topn(const cstripe_scan *s, uint64_t *n_groups, uint64_t *n_kept,
+        double *range_ms, double *select_ms, double *emit_ms);
+
 /* 1 when the last cstripe_scan_agg ran the fused decode+filter+aggregate
  * kernel (no scratch round trip), 0 for the two-kernel path */
 int cstripe_scan_last_fused(const cstripe_scan *s);
