@@ -133,6 +133,7 @@ struct cs_gpu_state {
     uint32_t max_zseg_dlen = 0;      /* largest zstd frame decompressed */
     zr_dtables *d_zrtab = nullptr;   /* predefined FSE decode tables */
     std::vector<uint8_t> col_scratch;/* per proj: any chunk lands in scratch */
+    bool any_zr = false;             /* some staged stream is zstd canonical */
     std::vector<uint8_t> col_ov;     /* per proj: every selected chunk group
                                       * holds it dense I64 canonical P(L) or
                                       * CONST (multi_agg_kernel_ov's shapes) */
@@ -1395,24 +1396,23 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel(
  * (distinct projected columns, predicate slots first), so a column is loaded
  * once per row group however many predicates and operands name it.
  *
- * A work item is one (chunk group, 2048-row tile): one R=8 row group per
- * lane. A fixed grid walks items blockIdx.x, +gridDim.x, ... with a plain
+ * A work item is one (chunk group, R*AGG_BLOCK-row tile), 2048 rows at R=8.
+ * Lane t holds rows t, t+256, ..., t+(R-1)*256 of the tile, so consecutive
+ * lanes hold consecutive rows and a wave's load covers 64*step contiguous
+ * bytes. A fixed grid walks items blockIdx.x, +gridDim.x, ... with a plain
  * for; every trip count follows from n_items. Per item:
- *   1. the predicate-slot windows (issued one item earlier) are extracted,
- *   2. the NEXT item's predicate-slot windows are issued back to back,
+ *   1. the predicate-slot dwords (issued one item earlier) are masked down,
+ *   2. the NEXT item's predicate-slot dwords are issued back to back,
  *   3. descriptors are fetched ahead (ColLoc two items, GroupDesc three),
  *   4. all predicates are evaluated from registers, each as one unsigned
  *      32-bit range test of the row's low word (ov_cmp); if any lane of the
- *      wave passes, the lanes that hold a passing row load the operand-only
- *      slots and fold their rows.
+ *      wave passes, the lanes that hold a passing row load those rows of the
+ *      operand-only slots and fold them.
  * The wait in (4) therefore covers this item's operands and the next item's
- * predicate windows together: one exposed round trip per item.
+ * predicate dwords together: one exposed round trip per item.
  *
- * A P(L) value is hval | low-L-bytes with L <= 4, so a row group is held as
- * 8 u32 per slot; windows are (7*step+4) bytes rounded up to u64 words —
- * never further than the (7*step+8) windows of col_multi for the same rows.
- * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
- * (canon_pos); the one lane holding row 0 fetches them beside its window.
+ * A P(L) value is hval | low-L-bytes with L <= 4, so a row is one u32 per
+ * slot: the unaligned dword at its closed-form position, masked (ov_load).
  * ===================================================================== */
 
 #define OV_R        8                    /* rows per lane per work item */
@@ -1420,8 +1420,6 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel(
                                           * half the registers per row group */
 #define OV_MAX_SLOTS 4
 #define OV_MAX_AGGS 4
-/* u64 words of the widest (step 7) window of an R-row group */
-#define OV_NW(R)    ((((R) - 1) * 7 + 4 + 7) / 8)
 
 struct OvPlan {
     uint32_t n_items;                    /* n_groups * tiles_pg */
@@ -1490,75 +1488,66 @@ __device__ inline uint32_t ov_mask(uint32_t step, uint32_t zr)
     return step == 0 ? 0u : 0xFFFFFFFFu >> ((4u - L) * 8u);
 }
 
-template <int R, uint32_t STEP>
-__device__ inline void ov_extract(const uint64_t (&w)[OV_NW(R)], uint32_t m,
-                                  uint32_t (&lo)[R])
+/* One slot's dwords for a tile: lane t takes rows row0 + k*AGG_BLOCK + t,
+ * k < R, so one load instruction of a wave covers 64*step contiguous bytes and
+ * the R loads walk the stream front to back, every line fetched once. A P(L)
+ * value has L <= 4 variable bytes, so the unaligned dword at the row's
+ * closed-form position (canon_pos) is the whole row: no neighbour word, no
+ * shift. The address is one wave-uniform base (stream + row0*step) plus a
+ * 32-bit lane offset that advances by AGG_BLOCK*step per k. Only row 0 of a
+ * stream sits off the closed form (lz4: +1, zstd: +15; lz4 row 1 is at
+ * 9 = off0 + step): a per-lane offset select for k == 0 of the group's first
+ * tile.
+ * rows: bit k set = load row k. The predicate slots pass the rows inside the
+ * group (all of them except in a group's last tile), the operand-only slots
+ * the rows that passed. There is one code path for both and for full and
+ * last tiles alike: two paths that load the same registers meet in a merge,
+ * a merge costs a copy, and a copy of a loaded register a wait right behind
+ * the load.
+ * Reach: a row whose bit is clear loads nothing, and a loaded row reads the
+ * 4 bytes at the position where the windowed bodies read 8, so this never
+ * reads a byte of a stream that they do not. */
+template <int R>
+__device__ inline void ov_load(const uint8_t *__restrict__ data, const OvCol &c,
+                               uint32_t row0, uint32_t rows, uint32_t (&w)[R])
 {
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    if (step == 0) return;                    /* CONST: no load, lo = 0 */
+    const uint8_t *sb = data + (ov_off(c) + (uint64_t)(row0 * step));
+    uint32_t vo = ov_off0(step, zr) + threadIdx.x * step;
+    const uint32_t vo0 = (row0 == 0 && threadIdx.x == 0) ? (zr ? 15u : 1u) : vo;
     #pragma unroll
     for (uint32_t k = 0; k < (uint32_t)R; k++) {
-        const uint32_t d = k * STEP, wi = d >> 3, sh = (d & 7u) * 8u;
-        uint32_t x = (uint32_t)(w[wi] >> sh);
-        if (sh > 32u) x |= (uint32_t)(w[wi + 1 < OV_NW(R) ? wi + 1 : wi] << (64u - sh));
-        lo[k] = x & m;
+        if ((rows >> k) & 1u)
+            __builtin_memcpy(&w[k], sb + (k == 0 ? vo0 : vo), 4);
+        vo += AGG_BLOCK * step;
     }
 }
 
-/* issue one slot's window for the lane's row group (row % R == 0, row inside
- * the chunk group). Every word is loaded straight into its final register
- * under a wave-uniform guard, never merged across branches: a merge would
- * cost a copy, and a copy of a loaded register a wait right behind the load.
- * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
- * (canon_pos). The one lane that holds row 0 points word 0 — which only
- * rows 0/1 of an lz4 window touch, step being >= 4 there — at lz4 row 0, and
- * loads lz4 row 1 / zstd row 0 into fx.
- * Word 0 is issued LAST and ov_take reads it on every path, so that one
- * read stands for "the whole window has landed" (loads return in order):
- * nothing of a window then counts as outstanding when the next one is
- * issued into the same registers, and no wait lands between the loads.
- * ALL (the operand-only slots, whose window is consumed at once): no guards
- * either — a surplus word re-reads the window's last word, so the reach is
- * the same and the extraction cannot be sunk in between the loads. */
-template <int R, bool ALL>
-__device__ inline void ov_issue(const uint8_t *__restrict__ data, const OvCol &c,
-                                uint32_t row, uint64_t (&w)[OV_NW(R)], uint32_t &fx)
-{
-    const uint32_t step = ov_step(c), zr = ov_zr(c);
-    if (step == 0) return;
-    const uint8_t *base = data + ov_off(c);
-    const uint8_t *p = base + (row * step + ov_off0(step, zr));
-    const uint32_t nbytes = (R - 1) * step + 4u;
-    if (row == 0) __builtin_memcpy(&fx, base + (zr ? 15u : 9u), 4);
-    const uint32_t lastw = (nbytes - 1u) >> 3;
-    #pragma unroll
-    for (uint32_t i = OV_NW(R) - 1; i >= 1; i--) {
-        if (ALL) __builtin_memcpy(&w[i], p + 8u * min(i, lastw), 8);
-        else if (8u * i < nbytes) __builtin_memcpy(&w[i], p + 8u * i, 8);
-    }
-    __builtin_memcpy(&w[0], (row == 0 && !zr) ? base + 1 : p, 8);
-    /* keep the scheduler from pulling a first use up between the loads */
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-/* window -> the row group's R low words (value = hval | low word) */
+/* bit k = row row0 + k*AGG_BLOCK + t lies inside the group (row0 < rc) */
 template <int R>
-__device__ inline void ov_take(const OvCol &c, uint32_t row,
-                               const uint64_t (&w)[OV_NW(R)], uint32_t fx,
-                               uint32_t (&lo)[R])
+__device__ inline uint32_t ov_rows(uint32_t row0, uint32_t rc)
 {
-    const uint32_t step = ov_step(c), zr = ov_zr(c);
-    const uint32_t m = ov_mask(step, zr);     /* CONST: any arm, all zero */
-    switch (step) {                           /* wave-uniform */
-        case 1: ov_extract<R, 1>(w, m, lo); break;
-        case 2: ov_extract<R, 2>(w, m, lo); break;
-        case 3: ov_extract<R, 3>(w, m, lo); break;
-        case 4: ov_extract<R, 4>(w, m, lo); break;
-        case 5: ov_extract<R, 5>(w, m, lo); break;
-        case 6: ov_extract<R, 6>(w, m, lo); break;
-        default: ov_extract<R, 7>(w, m, lo); break;
-    }
-    if (row == 0) {
-        if (zr) lo[0] = fx & m;
-        else    lo[1] = fx & m;
+    const uint32_t left = rc - row0;
+    uint32_t m = 0;
+    #pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)R; k++)
+        m |= (uint32_t)(k * AGG_BLOCK + threadIdx.x < left) << k;
+    return m;
+}
+
+/* dwords -> the rows' low words (value = hval | low word); CONST: all zero.
+ * The empty asm pins each AND here: left alone, the compiler sinks it to its
+ * first use, past the next item's loads, which then need a second register
+ * set and a copy per dword to keep w alive. */
+template <int R>
+__device__ inline void ov_lows(const OvCol &c, const uint32_t (&w)[R], uint32_t (&lo)[R])
+{
+    const uint32_t m = ov_mask(ov_step(c), ov_zr(c));
+    #pragma unroll
+    for (int k = 0; k < R; k++) {
+        lo[k] = w[k] & m;
+        asm volatile("" : "+v"(lo[k]));
     }
 }
 
@@ -1682,6 +1671,361 @@ __host__ __device__ constexpr uint32_t ov_ksig(uint32_t a, uint32_t kind)
 template <int R, int NS, int NPS, int NPREDS, int NAGGS, bool EXACT, int MINW,
           uint64_t SIG = 0, uint32_t KSIG = 0>
 __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
+    const uint8_t *__restrict__ data, const GroupDesc *__restrict__ groups,
+    const ColLoc *__restrict__ colloc, AccCell *__restrict__ block_out,
+    const AggParams params, const OvPlan plan)
+{
+    constexpr uint32_t TILE = R * AGG_BLOCK;
+    const uint32_t ns = EXACT ? (uint32_t)NS : plan.n_slots;
+    const uint32_t nps = EXACT ? (uint32_t)NPS : plan.n_pslots;
+    const uint32_t n_preds = EXACT ? (uint32_t)NPREDS : params.n_preds;
+    const uint32_t n_aggs = EXACT ? (uint32_t)NAGGS : params.n_aggs;
+    const uint32_t n_items = plan.n_items, tpg = plan.tiles_pg;
+    const uint32_t G = gridDim.x, last = n_items - 1u;
+
+    ThreadAcc acc[NAGGS];
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) ov_acc_init(acc[a], params.aggs[a].kind);
+
+    /* prologue: the block's first item, and the descriptors behind it */
+    uint32_t it = blockIdx.x;
+    OvCol c[NS] = {};
+    uint32_t crc = 0, crow = 0;          /* crow: the tile's first row, uniform */
+    uint32_t crows = 0;                  /* bit k = row crow + k*AGG_BLOCK + t exists */
+    /* zeroed word by word: an aggregate initialiser makes the whole array one
+     * 32-dword vector value, copied wholesale behind a full wait every trip */
+    uint32_t wn[NS][R];
+    #pragma unroll
+    for (int s = 0; s < NS; s++) {
+        #pragma unroll
+        for (int k = 0; k < R; k++) wn[s][k] = 0;
+    }
+    if (it < n_items) {
+        const GroupDesc g0 = groups[it / tpg];
+        crc = g0.row_count;
+        crow = (it % tpg) * TILE;
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < ns) c[s] = ov_col(ov_fetch(colloc[g0.colbase + plan.slot_proj[s]]));
+        if (crow < crc) crows = ov_rows<R>(crow, crc);
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < nps) ov_load<R>(data, c[s], crow, crows, wn[s]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    /* indices past the end are clamped for the descriptor reads only; an
+     * item that does not exist has an empty row mask and loads nothing */
+    const GroupDesc g1 = groups[min(it + G, last) / tpg];
+    OvCol nc[NS] = {};
+    #pragma unroll
+    for (int s = 0; s < NS; s++)
+        if ((uint32_t)s < ns) nc[s] = ov_col(ov_fetch(colloc[g1.colbase + plan.slot_proj[s]]));
+    uint32_t nrc = g1.row_count;
+    GroupDesc g2 = groups[min(it + 2u * G, last) / tpg];
+
+    for (; it < n_items; it += G) {
+        /* 1. this item's predicate slots: dwords -> R x u32 per slot */
+        uint32_t lo[NS][R];
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < nps) ov_lows<R>(c[s], wn[s], lo[s]);
+
+        /* 2. next item's predicate dwords, all slots back to back; only the
+         * last tile of a group has rows past row_count to mask, and an item
+         * that does not exist has no rows at all */
+        const uint32_t it1 = it + G;
+        const uint32_t nrow = (min(it1, last) % tpg) * TILE;
+        /* into a fresh value per trip (zero where nothing is loaded), not
+         * into wn: a dword that "keeps its old value" on some path is a
+         * merge, and the merge a copy per dword per trip. The zeroes are
+         * pinned here (empty asm) so that none is re-made between two
+         * guarded loads, where writing the register would have to wait for
+         * the loads in flight. */
+        uint32_t nw[NS][R];
+        #pragma unroll
+        for (int s = 0; s < NS; s++) {
+            #pragma unroll
+            for (int k = 0; k < R; k++) {
+                nw[s][k] = 0;
+                if ((uint32_t)s < nps) asm volatile("" : "+v"(nw[s][k]));
+            }
+        }
+        uint32_t nrows = 0;
+        if (it1 < n_items && nrow < nrc) nrows = ov_rows<R>(nrow, nrc);
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < nps) ov_load<R>(data, nc[s], nrow, nrows, nw[s]);
+        /* keep the scheduler from pulling a first use up between the loads */
+        __builtin_amdgcn_sched_barrier(0);
+
+        /* 3. descriptors: ColLocs of item +2 (its GroupDesc came one trip
+         * ago), GroupDesc of item +3 */
+        OvRaw nn[NS] = {};
+        #pragma unroll
+        for (int s = 0; s < NS; s++)
+            if ((uint32_t)s < ns) nn[s] = ov_fetch(colloc[g2.colbase + plan.slot_proj[s]]);
+        const uint32_t nnrc = g2.row_count;
+        const GroupDesc g3 = groups[min(it + 3u * G, last) / tpg];
+
+        /* 4. every predicate from registers; row-pass flags as a bitmask */
+        /* bit k = row crow + k*AGG_BLOCK + t */
+        uint32_t pv = crows;
+        uint32_t gv = 0;
+        #pragma unroll
+        for (uint32_t p = 0; p < (EXACT ? (uint32_t)NPREDS : n_preds); p++) {
+            const uint32_t ctl = plan.pred_ctl[p];
+            const int64_t ival = plan.pred_val[p];
+            uint32_t o[R]; uint64_t h = 0;
+            ov_pick<R, NS>(lo, c, EXACT ? (uint32_t)(SIG >> (2u * p)) & 3u
+                                        : ctl & 0xFFu, o, h);
+            const OvCmp cm = ov_cmp((ctl >> 8) & 0xFFu, h, ival);
+            uint32_t g = 0;
+            #pragma unroll
+            for (int k = 0; k < R; k++)
+                g |= (uint32_t)(o[k] - cm.a <= cm.d) << k;
+            gv |= g ^ ((0u - cm.inv) & ((1u << R) - 1u));
+            if (ctl >> 16) { pv &= gv; gv = 0; }
+        }
+
+        /* the wave-level test is the uniform branch round the whole fold;
+         * inside it only the lanes that hold a passing row go on (pv != 0
+         * implies the row exists): they alone load the operand-only slots, and of
+         * those only their passing rows, so a 128-B line no passing row
+         * lies in is never fetched, and a lane with nothing to add folds
+         * nothing. All loads of all operand slots are issued into distinct
+         * registers first, then waited for once; a row that did not pass
+         * has a zero word, and every fold skips it anyway. */
+        if (__ballot(pv != 0) != 0 && pv != 0) {
+            uint32_t ow[NS][R];
+            #pragma unroll
+            for (int s = 0; s < NS; s++) {
+                #pragma unroll
+                for (int k = 0; k < R; k++) ow[s][k] = 0;
+            }
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s >= nps && (uint32_t)s < ns)
+                    ov_load<R>(data, c[s], crow, pv, ow[s]);
+            __builtin_amdgcn_sched_barrier(0);
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s >= nps && (uint32_t)s < ns) ov_lows<R>(c[s], ow[s], lo[s]);
+            const int64_t cnt = __popc(pv);
+            #pragma unroll
+            for (int a = 0; a < NAGGS; a++) {
+                if (!EXACT && (uint32_t)a >= n_aggs) continue;
+                const AggD &g = params.aggs[a];
+                uint32_t oa[R], ob[R], oc[R];
+                uint64_t ha = 0, hb = 0, hc = 0;
+                const uint32_t sa = EXACT ? (uint32_t)(SIG >> (32u + 6u * a)) & 3u
+                                          : (uint32_t)plan.agg_slot[a][0];
+                const uint32_t sb = EXACT ? (uint32_t)(SIG >> (34u + 6u * a)) & 3u
+                                          : (uint32_t)plan.agg_slot[a][1];
+                const uint32_t sc = EXACT ? (uint32_t)(SIG >> (36u + 6u * a)) & 3u
+                                          : (uint32_t)plan.agg_slot[a][2];
+                const uint32_t kind = EXACT ? (KSIG >> (4u * a)) & 15u : (uint32_t)g.kind;
+                switch (kind) {                   /* values already in registers */
+                    case CSTRIPE_AGG_COUNT_STAR:
+                        acc[a].lo += cnt;
+                        break;
+                    case CSTRIPE_AGG_SUM_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u) t += (__int128)ov_val(oa[k], ha);
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    case CSTRIPE_AGG_MIN_I64:
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u) acc[a].lo = min(acc[a].lo, ov_val(oa[k], ha));
+                        break;
+                    case CSTRIPE_AGG_MAX_I64:
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u) acc[a].lo = max(acc[a].lo, ov_val(oa[k], ha));
+                        break;
+                    case CSTRIPE_AGG_SUM_PROD_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        if (EXACT && (ha | hb) == 0 &&
+                            __popc(ov_pick_mask<NS>(c, sa)) + __popc(ov_pick_mask<NS>(c, sb))
+                                <= OV_NARROW_BITS) {
+                            uint64_t u = 0;
+                            #pragma unroll
+                            for (int k = 0; k < R; k++)
+                                u += (uint64_t)ov_sel(pv, k, oa[k]) * ob[k];
+                            acc_add_i128(acc[a], (__int128)u);
+                            break;
+                        }
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u)
+                                t += (__int128)ov_val(oa[k], ha) * ov_val(ob[k], hb);
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    case CSTRIPE_AGG_SUM_DISC_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u)
+                                t += (__int128)ov_val(oa[k], ha) * (g.one - ov_val(ob[k], hb));
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    case CSTRIPE_AGG_SUM_DISC_TAX_I64: {
+                        ov_pick<R, NS>(lo, c, sa, oa, ha);
+                        ov_pick<R, NS>(lo, c, sb, ob, hb);
+                        ov_pick<R, NS>(lo, c, sc, oc, hc);
+                        __int128 t = 0;
+                        #pragma unroll
+                        for (int k = 0; k < R; k++)
+                            if ((pv >> k) & 1u)
+                                t += (__int128)ov_val(oa[k], ha) * (g.one - ov_val(ob[k], hb))
+                                     * (g.one + ov_val(oc[k], hc));
+                        acc_add_i128(acc[a], t);
+                        break;
+                    }
+                    default:
+                        break;
+                }
+                acc[a].cnt += cnt;
+            }
+        }
+
+        /* rotate the descriptor pipeline; the ColLocs fetched in (3) are
+         * first touched here, a whole fold later */
+        #pragma unroll
+        for (int s = 0; s < NS; s++) {
+            c[s] = nc[s]; nc[s] = ov_col(nn[s]);
+            #pragma unroll
+            for (int k = 0; k < R; k++) wn[s][k] = nw[s][k];
+        }
+        crc = nrc; crow = nrow; crows = nrows;
+        nrc = nnrc;
+        g2 = g3;
+    }
+
+    /* one wave/block reduce per block */
+    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][NAGGS];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    #pragma unroll
+    for (int a = 0; a < NAGGS; a++) {
+        if (!EXACT && (uint32_t)a >= n_aggs) continue;
+        wave_reduce(acc[a], params.aggs[a].kind);
+        if (lane == 0) lds[wid][a] = acc[a];
+    }
+    __syncthreads();
+    if (wid == 0) {
+        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
+            ThreadAcc r = lds[0][a];
+            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
+                acc_merge(r, lds[w][a], params.aggs[a].kind);
+            AccCell cell;
+            cell.lo = r.lo; cell.hi = r.hi; cell.f = r.f; cell.cnt = r.cnt;
+            block_out[(uint64_t)blockIdx.x * n_aggs + a] = cell;
+        }
+    }
+}
+
+/* =====================================================================
+ * The window form of the dense overlapped body, kept for scans over zstd
+ * canonical streams. There a row's low bytes are step = L = 1..4 bytes apart
+ * (lz4: L+3), so the per-lane 8-row window is one to four u64 words where the
+ * lane-contiguous form above issues eight dword loads per slot: on Q6 over
+ * 1B zstd rows the lane-contiguous form measured 2.84 ms against 2.74 ms
+ * for this one. Lane t holds rows R*t .. R*t+R-1 of the
+ * tile; everything outside the loads (plan, predicates, folds, reduce) is
+ * the same code.
+ * ===================================================================== */
+
+/* u64 words of the widest (step 7) window of an R-row group */
+#define OV_NW(R)    ((((R) - 1) * 7 + 4 + 7) / 8)
+
+template <int R, uint32_t STEP>
+__device__ inline void ov_extract(const uint64_t (&w)[OV_NW(R)], uint32_t m,
+                                  uint32_t (&lo)[R])
+{
+    #pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)R; k++) {
+        const uint32_t d = k * STEP, wi = d >> 3, sh = (d & 7u) * 8u;
+        uint32_t x = (uint32_t)(w[wi] >> sh);
+        if (sh > 32u) x |= (uint32_t)(w[wi + 1 < OV_NW(R) ? wi + 1 : wi] << (64u - sh));
+        lo[k] = x & m;
+    }
+}
+
+/* issue one slot's window for the lane's row group (row % R == 0, row inside
+ * the chunk group). Every word is loaded straight into its final register
+ * under a wave-uniform guard, never merged across branches: a merge would
+ * cost a copy, and a copy of a loaded register a wait right behind the load.
+ * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
+ * (canon_pos). The one lane that holds row 0 points word 0 — which only
+ * rows 0/1 of an lz4 window touch, step being >= 4 there — at lz4 row 0, and
+ * loads lz4 row 1 / zstd row 0 into fx.
+ * Word 0 is issued LAST and ov_take reads it on every path, so that one
+ * read stands for "the whole window has landed" (loads return in order):
+ * nothing of a window then counts as outstanding when the next one is
+ * issued into the same registers, and no wait lands between the loads.
+ * ALL (the operand-only slots, whose window is consumed at once): no guards
+ * either — a surplus word re-reads the window's last word, so the reach is
+ * the same and the extraction cannot be sunk in between the loads. */
+template <int R, bool ALL>
+__device__ inline void ov_issue(const uint8_t *__restrict__ data, const OvCol &c,
+                                uint32_t row, uint64_t (&w)[OV_NW(R)], uint32_t &fx)
+{
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    if (step == 0) return;
+    const uint8_t *base = data + ov_off(c);
+    const uint8_t *p = base + (row * step + ov_off0(step, zr));
+    const uint32_t nbytes = (R - 1) * step + 4u;
+    if (row == 0) __builtin_memcpy(&fx, base + (zr ? 15u : 9u), 4);
+    const uint32_t lastw = (nbytes - 1u) >> 3;
+    #pragma unroll
+    for (uint32_t i = OV_NW(R) - 1; i >= 1; i--) {
+        if (ALL) __builtin_memcpy(&w[i], p + 8u * min(i, lastw), 8);
+        else if (8u * i < nbytes) __builtin_memcpy(&w[i], p + 8u * i, 8);
+    }
+    __builtin_memcpy(&w[0], (row == 0 && !zr) ? base + 1 : p, 8);
+    /* keep the scheduler from pulling a first use up between the loads */
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+/* window -> the row group's R low words (value = hval | low word) */
+template <int R>
+__device__ inline void ov_take(const OvCol &c, uint32_t row,
+                               const uint64_t (&w)[OV_NW(R)], uint32_t fx,
+                               uint32_t (&lo)[R])
+{
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    const uint32_t m = ov_mask(step, zr);     /* CONST: any arm, all zero */
+    switch (step) {                           /* wave-uniform */
+        case 1: ov_extract<R, 1>(w, m, lo); break;
+        case 2: ov_extract<R, 2>(w, m, lo); break;
+        case 3: ov_extract<R, 3>(w, m, lo); break;
+        case 4: ov_extract<R, 4>(w, m, lo); break;
+        case 5: ov_extract<R, 5>(w, m, lo); break;
+        case 6: ov_extract<R, 6>(w, m, lo); break;
+        default: ov_extract<R, 7>(w, m, lo); break;
+    }
+    if (row == 0) {
+        if (zr) lo[0] = fx & m;
+        else    lo[1] = fx & m;
+    }
+}
+
+template <int R, int NS, int NPS, int NPREDS, int NAGGS, bool EXACT, int MINW,
+          uint64_t SIG = 0, uint32_t KSIG = 0>
+__global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ovw(
     const uint8_t *__restrict__ data, const GroupDesc *__restrict__ groups,
     const ColLoc *__restrict__ colloc, AccCell *__restrict__ block_out,
     const AggParams params, const OvPlan plan)
@@ -3807,8 +4151,10 @@ int csgpu_stage(cstripe_scan *s, int device_id)
     /* which projected columns the overlapped dense body can read: one pass
      * over the descriptors just built */
     g->col_ov.assign(n_proj, 1);
+    g->any_zr = false;
     for (uint64_t i = 0; i < h_colloc.size(); i++) {
         const ColLoc &cl = h_colloc[i];
+        if (cl.mode >= CSF_SEGMODE_ZRP_BASE) g->any_zr = true;
         const bool shape =
             cl.mode == CSF_SEGMODE_CONST || cl.mode == CSF_SEGMODE_ZR_CONST ||
             (((cl.mode & 0xF0u) == CSF_SEGMODE_P_BASE ||
@@ -5521,12 +5867,25 @@ static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
             constexpr uint32_t KSIG_Q6 = ov_ksig(0, CSTRIPE_AGG_SUM_PROD_I64) |
                                          ov_ksig(1, CSTRIPE_AGG_COUNT_STAR);
             constexpr uint32_t KSIG_CNT = ov_ksig(0, CSTRIPE_AGG_COUNT_STAR);
-            if (pl.n_slots == 4 && pl.n_pslots == 3 && p.n_preds == 5 && n_aggs == 2 &&
-                pl.sig == SIG_Q6 && pl.ksig == KSIG_Q6)
+            /* zstd streams (rows 1..4 bytes apart) keep the window form */
+            const bool q6 = pl.n_slots == 4 && pl.n_pslots == 3 && p.n_preds == 5 &&
+                            n_aggs == 2 && pl.sig == SIG_Q6 && pl.ksig == KSIG_Q6;
+            const bool cnt = pl.n_slots == 1 && p.n_preds == 1 && n_aggs == 1 &&
+                             pl.sig == 0 && pl.ksig == KSIG_CNT;
+            if (g->any_zr) {
+                if (q6)
+                    launcho(multi_agg_kernel_ovw<OV_R, 4, 3, 5, 2, true, OV_WAVES,
+                                                 SIG_Q6, KSIG_Q6>, OV_R);
+                else if (cnt)
+                    launcho(multi_agg_kernel_ovw<OV_R, 1, 1, 1, 1, true, OV_WAVES,
+                                                 0, KSIG_CNT>, OV_R);
+                else
+                    launcho(multi_agg_kernel_ovw<OV_R_ANY, OV_MAX_SLOTS, OV_MAX_SLOTS, 0,
+                                                 OV_MAX_AGGS, false, OV_WAVES>, OV_R_ANY);
+            } else if (q6)
                 launcho(multi_agg_kernel_ov<OV_R, 4, 3, 5, 2, true, OV_WAVES,
                                             SIG_Q6, KSIG_Q6>, OV_R);
-            else if (pl.n_slots == 1 && p.n_preds == 1 && n_aggs == 1 &&
-                     pl.sig == 0 && pl.ksig == KSIG_CNT)
+            else if (cnt)
                 launcho(multi_agg_kernel_ov<OV_R, 1, 1, 1, 1, true, OV_WAVES,
                                             0, KSIG_CNT>, OV_R);
             else
