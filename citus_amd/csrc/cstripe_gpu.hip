@@ -844,6 +844,37 @@ __device__ inline void wave_reduce(ThreadAcc &a, uint8_t kind)
     }
 }
 
+/* the ungrouped kernels' epilogue: wave reduce -> LDS -> wave 0 merges the
+ * waves -> one AccCell per aggregate per block, at block_out[block * n_aggs].
+ * NL is the LDS row length. UNROLL: the first pass is unrolled over the NA
+ * accumulators, guarded by n_aggs where that is no compile-time NA, so they
+ * stay in registers; otherwise it is a run-time loop over n_aggs. */
+template <int NL, bool UNROLL, int NA>
+__device__ __forceinline__ void block_reduce(ThreadAcc (&acc)[NA], const AggParams &params,
+                                             uint32_t n_aggs, AccCell *block_out)
+{
+    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][NL];
+    const uint32_t wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x % WAVE;
+    #pragma unroll
+    for (uint32_t a = 0; a < (UNROLL ? (uint32_t)NA : n_aggs); a++) {
+        if (UNROLL && a >= n_aggs) continue;
+        wave_reduce(acc[a], params.aggs[a].kind);
+        if (lane == 0) lds[wid][a] = acc[a];
+    }
+    __syncthreads();
+    if (wid == 0) {
+        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
+            ThreadAcc r = lds[0][a];
+            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
+                acc_merge(r, lds[w][a], params.aggs[a].kind);
+            AccCell c;
+            c.lo = r.lo; c.hi = r.hi; c.f = r.f; c.cnt = r.cnt;
+            block_out[(uint64_t)blockIdx.x * n_aggs + a] = c;
+        }
+    }
+}
+
 template <int NPREDS, int NAGGS>
 __global__ __launch_bounds__(AGG_BLOCK) void filter_agg_kernel(
     const uint8_t *__restrict__ data, const uint8_t *__restrict__ scratch,
@@ -890,26 +921,7 @@ __global__ __launch_bounds__(AGG_BLOCK) void filter_agg_kernel(
             acc_row(acc[a], params.aggs[a], data, scratch, rank, cols, row, true);
     }
 
-    /* wave reduce then cross-wave via LDS */
-    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][MAX_AGGS];
-    const uint32_t wid = threadIdx.x / WAVE;
-    const uint32_t lane = threadIdx.x % WAVE;
-    #pragma unroll
-    for (uint32_t a = 0; a < n_aggs; a++) {
-        wave_reduce(acc[a], params.aggs[a].kind);
-        if (lane == 0) lds[wid][a] = acc[a];
-    }
-    __syncthreads();
-    if (wid == 0) {
-        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
-            ThreadAcc r = lds[0][a];
-            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
-                acc_merge(r, lds[w][a], params.aggs[a].kind);
-            AccCell c;
-            c.lo = r.lo; c.hi = r.hi; c.f = r.f; c.cnt = r.cnt;
-            block_out[(uint64_t)blockIdx.x * n_aggs + a] = c;
-        }
-    }
+    block_reduce<MAX_AGGS, (NAGGS >= 0)>(acc, params, n_aggs, block_out);
 }
 
 
@@ -1003,26 +1015,7 @@ __global__ __launch_bounds__(AGG_BLOCK) void fused_agg_kernel(
         }
     }
 
-    /* reduce: wave shuffle -> cross-wave LDS -> one AccCell per block */
-    __shared__ ThreadAcc lred[AGG_BLOCK / WAVE][MAX_AGGS];
-    const uint32_t wid = tid / WAVE;
-    const uint32_t lane = tid % WAVE;
-    #pragma unroll
-    for (uint32_t a = 0; a < n_aggs; a++) {
-        wave_reduce(acc[a], params.aggs[a].kind);
-        if (lane == 0) lred[wid][a] = acc[a];
-    }
-    __syncthreads();
-    if (wid == 0) {
-        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
-            ThreadAcc r = lred[0][a];
-            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
-                acc_merge(r, lred[w][a], params.aggs[a].kind);
-            AccCell cell;
-            cell.lo = r.lo; cell.hi = r.hi; cell.f = r.f; cell.cnt = r.cnt;
-            block_out[(uint64_t)blockIdx.x * n_aggs + a] = cell;
-        }
-    }
+    block_reduce<MAX_AGGS, (NAGGS >= 0)>(acc, params, n_aggs, block_out);
 }
 
 /* ---- R-row variant (R=8): one (R-1)*step+8 <= 57 B window per column.
@@ -1368,25 +1361,7 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel(
             acc_multi<R>(acc[a], params.aggs[a], data, scratch, cols, row, pv);
     }
 
-    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][MAX_AGGS];
-    const uint32_t wid = threadIdx.x / WAVE;
-    const uint32_t lane = threadIdx.x % WAVE;
-    #pragma unroll
-    for (uint32_t a = 0; a < n_aggs; a++) {
-        wave_reduce(acc[a], params.aggs[a].kind);
-        if (lane == 0) lds[wid][a] = acc[a];
-    }
-    __syncthreads();
-    if (wid == 0) {
-        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
-            ThreadAcc r = lds[0][a];
-            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
-                acc_merge(r, lds[w][a], params.aggs[a].kind);
-            AccCell c;
-            c.lo = r.lo; c.hi = r.hi; c.f = r.f; c.cnt = r.cnt;
-            block_out[(uint64_t)blockIdx.x * n_aggs + a] = c;
-        }
-    }
+    block_reduce<MAX_AGGS, (NAGGS >= 0)>(acc, params, n_aggs, block_out);
 }
 
 /* =====================================================================
@@ -1664,11 +1639,100 @@ __host__ __device__ constexpr uint32_t ov_ksig(uint32_t a, uint32_t kind)
     return kind << (4u * a);
 }
 
-/* EXACT: the template counts, SIG and KSIG are the query's, so every slot
+/* ---------------------------------------------------------------------
+ * The window form of the loads, kept for scans over zstd canonical streams.
+ * There a row's low bytes are step = L = 1..4 bytes apart (lz4: L+3), so a
+ * per-lane 8-row window is one to four u64 words where the lane-contiguous
+ * form above issues eight dword loads per slot: on Q6 over 1B zstd rows the
+ * lane-contiguous form measured 2.84 ms against 2.74 ms for this one
+ * (DESIGN section 3). Lane t holds rows R*t .. R*t+R-1 of the tile.
+ * --------------------------------------------------------------------- */
+
+/* u64 words of the widest (step 7) window of an R-row group */
+#define OV_NW(R)    ((((R) - 1) * 7 + 4 + 7) / 8)
+
+template <int R, uint32_t STEP>
+__device__ inline void ov_extract(const uint64_t (&w)[OV_NW(R)], uint32_t m,
+                                  uint32_t (&lo)[R])
+{
+    #pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)R; k++) {
+        const uint32_t d = k * STEP, wi = d >> 3, sh = (d & 7u) * 8u;
+        uint32_t x = (uint32_t)(w[wi] >> sh);
+        if (sh > 32u) x |= (uint32_t)(w[wi + 1 < OV_NW(R) ? wi + 1 : wi] << (64u - sh));
+        lo[k] = x & m;
+    }
+}
+
+/* issue one slot's window for the lane's row group (row % R == 0, row inside
+ * the chunk group). Every word is loaded straight into its final register
+ * under a wave-uniform guard, never merged across branches: a merge would
+ * cost a copy, and a copy of a loaded register a wait right behind the load.
+ * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
+ * (canon_pos). The one lane that holds row 0 points word 0 — which only
+ * rows 0/1 of an lz4 window touch, step being >= 4 there — at lz4 row 0, and
+ * loads lz4 row 1 / zstd row 0 into fx.
+ * Word 0 is issued LAST and ov_take reads it on every path, so that one
+ * read stands for "the whole window has landed" (loads return in order):
+ * nothing of a window then counts as outstanding when the next one is
+ * issued into the same registers, and no wait lands between the loads.
+ * ALL (the operand-only slots, whose window is consumed at once): no guards
+ * either — a surplus word re-reads the window's last word, so the reach is
+ * the same and the extraction cannot be sunk in between the loads. */
+template <int R, bool ALL>
+__device__ inline void ov_issue(const uint8_t *__restrict__ data, const OvCol &c,
+                                uint32_t row, uint64_t (&w)[OV_NW(R)], uint32_t &fx)
+{
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    if (step == 0) return;
+    const uint8_t *base = data + ov_off(c);
+    const uint8_t *p = base + (row * step + ov_off0(step, zr));
+    const uint32_t nbytes = (R - 1) * step + 4u;
+    if (row == 0) __builtin_memcpy(&fx, base + (zr ? 15u : 9u), 4);
+    const uint32_t lastw = (nbytes - 1u) >> 3;
+    #pragma unroll
+    for (uint32_t i = OV_NW(R) - 1; i >= 1; i--) {
+        if (ALL) __builtin_memcpy(&w[i], p + 8u * min(i, lastw), 8);
+        else if (8u * i < nbytes) __builtin_memcpy(&w[i], p + 8u * i, 8);
+    }
+    __builtin_memcpy(&w[0], (row == 0 && !zr) ? base + 1 : p, 8);
+    /* keep the scheduler from pulling a first use up between the loads */
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+/* window -> the row group's R low words (value = hval | low word) */
+template <int R>
+__device__ inline void ov_take(const OvCol &c, uint32_t row,
+                               const uint64_t (&w)[OV_NW(R)], uint32_t fx,
+                               uint32_t (&lo)[R])
+{
+    const uint32_t step = ov_step(c), zr = ov_zr(c);
+    const uint32_t m = ov_mask(step, zr);     /* CONST: any arm, all zero */
+    switch (step) {                           /* wave-uniform */
+        case 1: ov_extract<R, 1>(w, m, lo); break;
+        case 2: ov_extract<R, 2>(w, m, lo); break;
+        case 3: ov_extract<R, 3>(w, m, lo); break;
+        case 4: ov_extract<R, 4>(w, m, lo); break;
+        case 5: ov_extract<R, 5>(w, m, lo); break;
+        case 6: ov_extract<R, 6>(w, m, lo); break;
+        default: ov_extract<R, 7>(w, m, lo); break;
+    }
+    if (row == 0) {
+        if (zr) lo[0] = fx & m;
+        else    lo[1] = fx & m;
+    }
+}
+
+/* WIN: the window form of the loads (ov_issue / ov_take), else the
+ * lane-contiguous form (ov_rows / ov_load / ov_lows). Only the loads, the
+ * initial row mask and the rotate of the loaded words differ, each under an
+ * if constexpr below; the plan, the descriptor pipeline, the predicates, the
+ * folds and the reduce exist once.
+ * EXACT: the template counts, SIG and KSIG are the query's, so every slot
  * and kind below is a compile-time constant; otherwise the counts are
  * capacities and everything comes from the plan / params through
  * wave-uniform guards */
-template <int R, int NS, int NPS, int NPREDS, int NAGGS, bool EXACT, int MINW,
+template <bool WIN, int R, int NS, int NPS, int NPREDS, int NAGGS, bool EXACT, int MINW,
           uint64_t SIG = 0, uint32_t KSIG = 0>
 __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
     const uint8_t *__restrict__ data, const GroupDesc *__restrict__ groups,
@@ -1682,6 +1746,9 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
     const uint32_t n_aggs = EXACT ? (uint32_t)NAGGS : params.n_aggs;
     const uint32_t n_items = plan.n_items, tpg = plan.tiles_pg;
     const uint32_t G = gridDim.x, last = n_items - 1u;
+    /* the lane's first row within a tile: the window form gives lane t rows
+     * R*t .. R*t+R-1, the lane form rows t + k*AGG_BLOCK off a uniform base */
+    const uint32_t lrow = WIN ? R * threadIdx.x : 0u;
 
     ThreadAcc acc[NAGGS];
     #pragma unroll
@@ -1690,31 +1757,49 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
     /* prologue: the block's first item, and the descriptors behind it */
     uint32_t it = blockIdx.x;
     OvCol c[NS] = {};
-    uint32_t crc = 0, crow = 0;          /* crow: the tile's first row, uniform */
-    uint32_t crows = 0;                  /* bit k = row crow + k*AGG_BLOCK + t exists */
-    /* zeroed word by word: an aggregate initialiser makes the whole array one
-     * 32-dword vector value, copied wholesale behind a full wait every trip */
+    /* crow: the lane's first row (window form), the tile's first row, uniform
+     * (lane form) */
+    uint32_t crc = 0, crow = 0;
+    /* both forms' load state is declared here so that it reaches the rotate;
+     * the form not instantiated never uses its half, which dies.
+     * Lane form: crows, bit k = row crow + k*AGG_BLOCK + t exists, and the
+     * dwords wn, zeroed word by word: an aggregate initialiser makes the whole
+     * array one 32-dword vector value, copied wholesale behind a full wait
+     * every trip.
+     * Window form: the windows ww and the off-form rows fx (ov_issue). */
+    uint32_t crows = 0;
     uint32_t wn[NS][R];
     #pragma unroll
     for (int s = 0; s < NS; s++) {
         #pragma unroll
         for (int k = 0; k < R; k++) wn[s][k] = 0;
     }
+    uint64_t ww[NS][OV_NW(R)] = {};
+    uint32_t fx[NS] = {};
     if (it < n_items) {
         const GroupDesc g0 = groups[it / tpg];
         crc = g0.row_count;
-        crow = (it % tpg) * TILE;
+        crow = (it % tpg) * TILE + lrow;
         #pragma unroll
         for (int s = 0; s < NS; s++)
             if ((uint32_t)s < ns) c[s] = ov_col(ov_fetch(colloc[g0.colbase + plan.slot_proj[s]]));
-        if (crow < crc) crows = ov_rows<R>(crow, crc);
-        #pragma unroll
-        for (int s = 0; s < NS; s++)
-            if ((uint32_t)s < nps) ov_load<R>(data, c[s], crow, crows, wn[s]);
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (WIN) {
+            if (crow < crc) {
+                #pragma unroll
+                for (int s = 0; s < NS; s++)
+                    if ((uint32_t)s < nps) ov_issue<R, false>(data, c[s], crow, ww[s], fx[s]);
+            }
+        } else {
+            if (crow < crc) crows = ov_rows<R>(crow, crc);
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s < nps) ov_load<R>(data, c[s], crow, crows, wn[s]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
     /* indices past the end are clamped for the descriptor reads only; an
-     * item that does not exist has an empty row mask and loads nothing */
+     * item that does not exist has an empty row mask (lane form) or no
+     * window issued (window form) and loads nothing */
     const GroupDesc g1 = groups[min(it + G, last) / tpg];
     OvCol nc[NS] = {};
     #pragma unroll
@@ -1724,39 +1809,51 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
     GroupDesc g2 = groups[min(it + 2u * G, last) / tpg];
 
     for (; it < n_items; it += G) {
-        /* 1. this item's predicate slots: dwords -> R x u32 per slot */
+        /* 1. this item's predicate slots: windows / dwords -> R x u32 per slot */
         uint32_t lo[NS][R];
         #pragma unroll
         for (int s = 0; s < NS; s++)
-            if ((uint32_t)s < nps) ov_lows<R>(c[s], wn[s], lo[s]);
-
-        /* 2. next item's predicate dwords, all slots back to back; only the
-         * last tile of a group has rows past row_count to mask, and an item
-         * that does not exist has no rows at all */
-        const uint32_t it1 = it + G;
-        const uint32_t nrow = (min(it1, last) % tpg) * TILE;
-        /* into a fresh value per trip (zero where nothing is loaded), not
-         * into wn: a dword that "keeps its old value" on some path is a
-         * merge, and the merge a copy per dword per trip. The zeroes are
-         * pinned here (empty asm) so that none is re-made between two
-         * guarded loads, where writing the register would have to wait for
-         * the loads in flight. */
-        uint32_t nw[NS][R];
-        #pragma unroll
-        for (int s = 0; s < NS; s++) {
-            #pragma unroll
-            for (int k = 0; k < R; k++) {
-                nw[s][k] = 0;
-                if ((uint32_t)s < nps) asm volatile("" : "+v"(nw[s][k]));
+            if ((uint32_t)s < nps) {
+                if constexpr (WIN) ov_take<R>(c[s], crow, ww[s], fx[s], lo[s]);
+                else ov_lows<R>(c[s], wn[s], lo[s]);
             }
-        }
+
+        /* 2. next item's predicate windows / dwords, all slots back to back */
+        const uint32_t it1 = it + G;
+        const uint32_t nrow = (min(it1, last) % tpg) * TILE + lrow;
+        uint32_t nw[NS][R];
         uint32_t nrows = 0;
-        if (it1 < n_items && nrow < nrc) nrows = ov_rows<R>(nrow, nrc);
-        #pragma unroll
-        for (int s = 0; s < NS; s++)
-            if ((uint32_t)s < nps) ov_load<R>(data, nc[s], nrow, nrows, nw[s]);
-        /* keep the scheduler from pulling a first use up between the loads */
-        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (WIN) {
+            /* straight into ww / fx: ov_take has read word 0 of every window */
+            if (it1 < n_items && nrow < nrc) {
+                #pragma unroll
+                for (int s = 0; s < NS; s++)
+                    if ((uint32_t)s < nps) ov_issue<R, false>(data, nc[s], nrow, ww[s], fx[s]);
+            }
+        } else {
+            /* only the last tile of a group has rows past row_count to mask,
+             * and an item that does not exist has no rows at all.
+             * Into a fresh value per trip (zero where nothing is loaded), not
+             * into wn: a dword that "keeps its old value" on some path is a
+             * merge, and the merge a copy per dword per trip. The zeroes are
+             * pinned here (empty asm) so that none is re-made between two
+             * guarded loads, where writing the register would have to wait for
+             * the loads in flight. */
+            #pragma unroll
+            for (int s = 0; s < NS; s++) {
+                #pragma unroll
+                for (int k = 0; k < R; k++) {
+                    nw[s][k] = 0;
+                    if ((uint32_t)s < nps) asm volatile("" : "+v"(nw[s][k]));
+                }
+            }
+            if (it1 < n_items && nrow < nrc) nrows = ov_rows<R>(nrow, nrc);
+            #pragma unroll
+            for (int s = 0; s < NS; s++)
+                if ((uint32_t)s < nps) ov_load<R>(data, nc[s], nrow, nrows, nw[s]);
+            /* keep the scheduler from pulling a first use up between the loads */
+            __builtin_amdgcn_sched_barrier(0);
+        }
 
         /* 3. descriptors: ColLocs of item +2 (its GroupDesc came one trip
          * ago), GroupDesc of item +3 */
@@ -1768,8 +1865,16 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
         const GroupDesc g3 = groups[min(it + 3u * G, last) / tpg];
 
         /* 4. every predicate from registers; row-pass flags as a bitmask */
-        /* bit k = row crow + k*AGG_BLOCK + t */
+        /* bit k = the lane's row k: crow + k (window form), crow +
+         * k*AGG_BLOCK + t (lane form); set = the row lies inside the group */
         uint32_t pv = crows;
+        if constexpr (WIN) {
+            pv = 0;
+            if (crow < crc) {
+                const uint32_t left = crc - crow;
+                pv = left >= (uint32_t)R ? (1u << R) - 1u : (1u << left) - 1u;
+            }
+        }
         uint32_t gv = 0;
         #pragma unroll
         for (uint32_t p = 0; p < (EXACT ? (uint32_t)NPREDS : n_preds); p++) {
@@ -1789,27 +1894,42 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
 
         /* the wave-level test is the uniform branch round the whole fold;
          * inside it only the lanes that hold a passing row go on (pv != 0
-         * implies the row exists): they alone load the operand-only slots, and of
-         * those only their passing rows, so a 128-B line no passing row
-         * lies in is never fetched, and a lane with nothing to add folds
-         * nothing. All loads of all operand slots are issued into distinct
-         * registers first, then waited for once; a row that did not pass
-         * has a zero word, and every fold skips it anyway. */
+         * implies the row exists): they alone load the operand-only slots,
+         * so a 128-B line no passing lane reaches is never fetched, and a
+         * lane with nothing to add folds nothing. */
         if (__ballot(pv != 0) != 0 && pv != 0) {
-            uint32_t ow[NS][R];
-            #pragma unroll
-            for (int s = 0; s < NS; s++) {
+            if constexpr (WIN) {
+                /* the lane's whole window, consumed at once */
                 #pragma unroll
-                for (int k = 0; k < R; k++) ow[s][k] = 0;
+                for (int s = 0; s < NS; s++)
+                    if ((uint32_t)s >= nps && (uint32_t)s < ns) {
+                        uint64_t w[OV_NW(R)] = {};
+                        uint32_t f = 0;
+                        ov_issue<R, true>(data, c[s], crow, w, f);
+                        ov_take<R>(c[s], crow, w, f, lo[s]);
+                    }
+            } else {
+                /* only the lane's passing rows, so not even a line that no
+                 * passing row lies in. All loads of all operand slots are
+                 * issued into distinct registers first, then waited for
+                 * once; a row that did not pass has a zero word, and every
+                 * fold skips it anyway. */
+                uint32_t ow[NS][R];
+                #pragma unroll
+                for (int s = 0; s < NS; s++) {
+                    #pragma unroll
+                    for (int k = 0; k < R; k++) ow[s][k] = 0;
+                }
+                #pragma unroll
+                for (int s = 0; s < NS; s++)
+                    if ((uint32_t)s >= nps && (uint32_t)s < ns)
+                        ov_load<R>(data, c[s], crow, pv, ow[s]);
+                __builtin_amdgcn_sched_barrier(0);
+                #pragma unroll
+                for (int s = 0; s < NS; s++)
+                    if ((uint32_t)s >= nps && (uint32_t)s < ns)
+                        ov_lows<R>(c[s], ow[s], lo[s]);
             }
-            #pragma unroll
-            for (int s = 0; s < NS; s++)
-                if ((uint32_t)s >= nps && (uint32_t)s < ns)
-                    ov_load<R>(data, c[s], crow, pv, ow[s]);
-            __builtin_amdgcn_sched_barrier(0);
-            #pragma unroll
-            for (int s = 0; s < NS; s++)
-                if ((uint32_t)s >= nps && (uint32_t)s < ns) ov_lows<R>(c[s], ow[s], lo[s]);
             const int64_t cnt = __popc(pv);
             #pragma unroll
             for (int a = 0; a < NAGGS; a++) {
@@ -1906,356 +2026,19 @@ __global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ov(
         #pragma unroll
         for (int s = 0; s < NS; s++) {
             c[s] = nc[s]; nc[s] = ov_col(nn[s]);
-            #pragma unroll
-            for (int k = 0; k < R; k++) wn[s][k] = nw[s][k];
-        }
-        crc = nrc; crow = nrow; crows = nrows;
-        nrc = nnrc;
-        g2 = g3;
-    }
-
-    /* one wave/block reduce per block */
-    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][NAGGS];
-    const uint32_t wid = threadIdx.x / WAVE;
-    const uint32_t lane = threadIdx.x % WAVE;
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++) {
-        if (!EXACT && (uint32_t)a >= n_aggs) continue;
-        wave_reduce(acc[a], params.aggs[a].kind);
-        if (lane == 0) lds[wid][a] = acc[a];
-    }
-    __syncthreads();
-    if (wid == 0) {
-        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
-            ThreadAcc r = lds[0][a];
-            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
-                acc_merge(r, lds[w][a], params.aggs[a].kind);
-            AccCell cell;
-            cell.lo = r.lo; cell.hi = r.hi; cell.f = r.f; cell.cnt = r.cnt;
-            block_out[(uint64_t)blockIdx.x * n_aggs + a] = cell;
-        }
-    }
-}
-
-/* =====================================================================
- * The window form of the dense overlapped body, kept for scans over zstd
- * canonical streams. There a row's low bytes are step = L = 1..4 bytes apart
- * (lz4: L+3), so the per-lane 8-row window is one to four u64 words where the
- * lane-contiguous form above issues eight dword loads per slot: on Q6 over
- * 1B zstd rows the lane-contiguous form measured 2.84 ms against 2.74 ms
- * for this one. Lane t holds rows R*t .. R*t+R-1 of the
- * tile; everything outside the loads (plan, predicates, folds, reduce) is
- * the same code.
- * ===================================================================== */
-
-/* u64 words of the widest (step 7) window of an R-row group */
-#define OV_NW(R)    ((((R) - 1) * 7 + 4 + 7) / 8)
-
-template <int R, uint32_t STEP>
-__device__ inline void ov_extract(const uint64_t (&w)[OV_NW(R)], uint32_t m,
-                                  uint32_t (&lo)[R])
-{
-    #pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)R; k++) {
-        const uint32_t d = k * STEP, wi = d >> 3, sh = (d & 7u) * 8u;
-        uint32_t x = (uint32_t)(w[wi] >> sh);
-        if (sh > 32u) x |= (uint32_t)(w[wi + 1 < OV_NW(R) ? wi + 1 : wi] << (64u - sh));
-        lo[k] = x & m;
-    }
-}
-
-/* issue one slot's window for the lane's row group (row % R == 0, row inside
- * the chunk group). Every word is loaded straight into its final register
- * under a wave-uniform guard, never merged across branches: a merge would
- * cost a copy, and a copy of a loaded register a wait right behind the load.
- * Rows 0/1 of an lz4 stream and row 0 of a zstd one sit at their own offsets
- * (canon_pos). The one lane that holds row 0 points word 0 — which only
- * rows 0/1 of an lz4 window touch, step being >= 4 there — at lz4 row 0, and
- * loads lz4 row 1 / zstd row 0 into fx.
- * Word 0 is issued LAST and ov_take reads it on every path, so that one
- * read stands for "the whole window has landed" (loads return in order):
- * nothing of a window then counts as outstanding when the next one is
- * issued into the same registers, and no wait lands between the loads.
- * ALL (the operand-only slots, whose window is consumed at once): no guards
- * either — a surplus word re-reads the window's last word, so the reach is
- * the same and the extraction cannot be sunk in between the loads. */
-template <int R, bool ALL>
-__device__ inline void ov_issue(const uint8_t *__restrict__ data, const OvCol &c,
-                                uint32_t row, uint64_t (&w)[OV_NW(R)], uint32_t &fx)
-{
-    const uint32_t step = ov_step(c), zr = ov_zr(c);
-    if (step == 0) return;
-    const uint8_t *base = data + ov_off(c);
-    const uint8_t *p = base + (row * step + ov_off0(step, zr));
-    const uint32_t nbytes = (R - 1) * step + 4u;
-    if (row == 0) __builtin_memcpy(&fx, base + (zr ? 15u : 9u), 4);
-    const uint32_t lastw = (nbytes - 1u) >> 3;
-    #pragma unroll
-    for (uint32_t i = OV_NW(R) - 1; i >= 1; i--) {
-        if (ALL) __builtin_memcpy(&w[i], p + 8u * min(i, lastw), 8);
-        else if (8u * i < nbytes) __builtin_memcpy(&w[i], p + 8u * i, 8);
-    }
-    __builtin_memcpy(&w[0], (row == 0 && !zr) ? base + 1 : p, 8);
-    /* keep the scheduler from pulling a first use up between the loads */
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-/* window -> the row group's R low words (value = hval | low word) */
-template <int R>
-__device__ inline void ov_take(const OvCol &c, uint32_t row,
-                               const uint64_t (&w)[OV_NW(R)], uint32_t fx,
-                               uint32_t (&lo)[R])
-{
-    const uint32_t step = ov_step(c), zr = ov_zr(c);
-    const uint32_t m = ov_mask(step, zr);     /* CONST: any arm, all zero */
-    switch (step) {                           /* wave-uniform */
-        case 1: ov_extract<R, 1>(w, m, lo); break;
-        case 2: ov_extract<R, 2>(w, m, lo); break;
-        case 3: ov_extract<R, 3>(w, m, lo); break;
-        case 4: ov_extract<R, 4>(w, m, lo); break;
-        case 5: ov_extract<R, 5>(w, m, lo); break;
-        case 6: ov_extract<R, 6>(w, m, lo); break;
-        default: ov_extract<R, 7>(w, m, lo); break;
-    }
-    if (row == 0) {
-        if (zr) lo[0] = fx & m;
-        else    lo[1] = fx & m;
-    }
-}
-
-template <int R, int NS, int NPS, int NPREDS, int NAGGS, bool EXACT, int MINW,
-          uint64_t SIG = 0, uint32_t KSIG = 0>
-__global__ __launch_bounds__(AGG_BLOCK, MINW) void multi_agg_kernel_ovw(
-    const uint8_t *__restrict__ data, const GroupDesc *__restrict__ groups,
-    const ColLoc *__restrict__ colloc, AccCell *__restrict__ block_out,
-    const AggParams params, const OvPlan plan)
-{
-    constexpr uint32_t TILE = R * AGG_BLOCK;
-    const uint32_t ns = EXACT ? (uint32_t)NS : plan.n_slots;
-    const uint32_t nps = EXACT ? (uint32_t)NPS : plan.n_pslots;
-    const uint32_t n_preds = EXACT ? (uint32_t)NPREDS : params.n_preds;
-    const uint32_t n_aggs = EXACT ? (uint32_t)NAGGS : params.n_aggs;
-    const uint32_t n_items = plan.n_items, tpg = plan.tiles_pg;
-    const uint32_t G = gridDim.x, last = n_items - 1u;
-    const uint32_t lrow = R * threadIdx.x;
-
-    ThreadAcc acc[NAGGS];
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++) ov_acc_init(acc[a], params.aggs[a].kind);
-
-    /* prologue: the block's first item, and the descriptors behind it */
-    uint32_t it = blockIdx.x;
-    OvCol c[NS] = {};
-    uint32_t crc = 0, crow = 0;
-    uint64_t wn[NS][OV_NW(R)] = {};
-    uint32_t fx[NS] = {};
-    if (it < n_items) {
-        const GroupDesc g0 = groups[it / tpg];
-        crc = g0.row_count;
-        crow = (it % tpg) * TILE + lrow;
-        #pragma unroll
-        for (int s = 0; s < NS; s++)
-            if ((uint32_t)s < ns) c[s] = ov_col(ov_fetch(colloc[g0.colbase + plan.slot_proj[s]]));
-        if (crow < crc) {
-            #pragma unroll
-            for (int s = 0; s < NS; s++)
-                if ((uint32_t)s < nps) ov_issue<R, false>(data, c[s], crow, wn[s], fx[s]);
-        }
-    }
-    /* indices past the end are clamped for the descriptor reads only; no
-     * window is ever issued for an item that does not exist */
-    const GroupDesc g1 = groups[min(it + G, last) / tpg];
-    OvCol nc[NS] = {};
-    #pragma unroll
-    for (int s = 0; s < NS; s++)
-        if ((uint32_t)s < ns) nc[s] = ov_col(ov_fetch(colloc[g1.colbase + plan.slot_proj[s]]));
-    uint32_t nrc = g1.row_count;
-    GroupDesc g2 = groups[min(it + 2u * G, last) / tpg];
-
-    for (; it < n_items; it += G) {
-        /* 1. this item's predicate slots: windows -> R x u32 per slot */
-        uint32_t lo[NS][R];
-        const bool active = crow < crc;
-        #pragma unroll
-        for (int s = 0; s < NS; s++)
-            if ((uint32_t)s < nps) ov_take<R>(c[s], crow, wn[s], fx[s], lo[s]);
-
-        /* 2. next item's predicate windows, all slots back to back */
-        const uint32_t it1 = it + G;
-        const uint32_t nrow = (min(it1, last) % tpg) * TILE + lrow;
-        if (it1 < n_items && nrow < nrc) {
-            #pragma unroll
-            for (int s = 0; s < NS; s++)
-                if ((uint32_t)s < nps) ov_issue<R, false>(data, nc[s], nrow, wn[s], fx[s]);
-        }
-
-        /* 3. descriptors: ColLocs of item +2 (its GroupDesc came one trip
-         * ago), GroupDesc of item +3 */
-        OvRaw nn[NS] = {};
-        #pragma unroll
-        for (int s = 0; s < NS; s++)
-            if ((uint32_t)s < ns) nn[s] = ov_fetch(colloc[g2.colbase + plan.slot_proj[s]]);
-        const uint32_t nnrc = g2.row_count;
-        const GroupDesc g3 = groups[min(it + 3u * G, last) / tpg];
-
-        /* 4. every predicate from registers; row-pass flags as a bitmask */
-        uint32_t pv = 0;
-        if (active) {
-            const uint32_t left = crc - crow;
-            pv = left >= (uint32_t)R ? (1u << R) - 1u : (1u << left) - 1u;
-        }
-        uint32_t gv = 0;
-        #pragma unroll
-        for (uint32_t p = 0; p < (EXACT ? (uint32_t)NPREDS : n_preds); p++) {
-            const uint32_t ctl = plan.pred_ctl[p];
-            const int64_t ival = plan.pred_val[p];
-            uint32_t o[R]; uint64_t h = 0;
-            ov_pick<R, NS>(lo, c, EXACT ? (uint32_t)(SIG >> (2u * p)) & 3u
-                                        : ctl & 0xFFu, o, h);
-            const OvCmp cm = ov_cmp((ctl >> 8) & 0xFFu, h, ival);
-            uint32_t g = 0;
-            #pragma unroll
-            for (int k = 0; k < R; k++)
-                g |= (uint32_t)(o[k] - cm.a <= cm.d) << k;
-            gv |= g ^ ((0u - cm.inv) & ((1u << R) - 1u));
-            if (ctl >> 16) { pv &= gv; gv = 0; }
-        }
-
-        /* the wave-level test is the uniform branch round the whole fold;
-         * inside it only the lanes that hold a passing row go on (pv != 0
-         * implies active): they alone load the operand-only slots, so a
-         * 128-B line no passing lane reaches is never fetched, and a lane
-         * with nothing to add folds nothing */
-        if (__ballot(pv != 0) != 0 && pv != 0) {
-            #pragma unroll
-            for (int s = 0; s < NS; s++)
-                if ((uint32_t)s >= nps && (uint32_t)s < ns) {
-                    uint64_t w[OV_NW(R)] = {};
-                    uint32_t f = 0;
-                    ov_issue<R, true>(data, c[s], crow, w, f);
-                    ov_take<R>(c[s], crow, w, f, lo[s]);
-                }
-            const int64_t cnt = __popc(pv);
-            #pragma unroll
-            for (int a = 0; a < NAGGS; a++) {
-                if (!EXACT && (uint32_t)a >= n_aggs) continue;
-                const AggD &g = params.aggs[a];
-                uint32_t oa[R], ob[R], oc[R];
-                uint64_t ha = 0, hb = 0, hc = 0;
-                const uint32_t sa = EXACT ? (uint32_t)(SIG >> (32u + 6u * a)) & 3u
-                                          : (uint32_t)plan.agg_slot[a][0];
-                const uint32_t sb = EXACT ? (uint32_t)(SIG >> (34u + 6u * a)) & 3u
-                                          : (uint32_t)plan.agg_slot[a][1];
-                const uint32_t sc = EXACT ? (uint32_t)(SIG >> (36u + 6u * a)) & 3u
-                                          : (uint32_t)plan.agg_slot[a][2];
-                const uint32_t kind = EXACT ? (KSIG >> (4u * a)) & 15u : (uint32_t)g.kind;
-                switch (kind) {                   /* values already in registers */
-                    case CSTRIPE_AGG_COUNT_STAR:
-                        acc[a].lo += cnt;
-                        break;
-                    case CSTRIPE_AGG_SUM_I64: {
-                        ov_pick<R, NS>(lo, c, sa, oa, ha);
-                        __int128 t = 0;
-                        #pragma unroll
-                        for (int k = 0; k < R; k++)
-                            if ((pv >> k) & 1u) t += (__int128)ov_val(oa[k], ha);
-                        acc_add_i128(acc[a], t);
-                        break;
-                    }
-                    case CSTRIPE_AGG_MIN_I64:
-                        ov_pick<R, NS>(lo, c, sa, oa, ha);
-                        #pragma unroll
-                        for (int k = 0; k < R; k++)
-                            if ((pv >> k) & 1u) acc[a].lo = min(acc[a].lo, ov_val(oa[k], ha));
-                        break;
-                    case CSTRIPE_AGG_MAX_I64:
-                        ov_pick<R, NS>(lo, c, sa, oa, ha);
-                        #pragma unroll
-                        for (int k = 0; k < R; k++)
-                            if ((pv >> k) & 1u) acc[a].lo = max(acc[a].lo, ov_val(oa[k], ha));
-                        break;
-                    case CSTRIPE_AGG_SUM_PROD_I64: {
-                        ov_pick<R, NS>(lo, c, sa, oa, ha);
-                        ov_pick<R, NS>(lo, c, sb, ob, hb);
-                        if (EXACT && (ha | hb) == 0 &&
-                            __popc(ov_pick_mask<NS>(c, sa)) + __popc(ov_pick_mask<NS>(c, sb))
-                                <= OV_NARROW_BITS) {
-                            uint64_t u = 0;
-                            #pragma unroll
-                            for (int k = 0; k < R; k++)
-                                u += (uint64_t)ov_sel(pv, k, oa[k]) * ob[k];
-                            acc_add_i128(acc[a], (__int128)u);
-                            break;
-                        }
-                        __int128 t = 0;
-                        #pragma unroll
-                        for (int k = 0; k < R; k++)
-                            if ((pv >> k) & 1u)
-                                t += (__int128)ov_val(oa[k], ha) * ov_val(ob[k], hb);
-                        acc_add_i128(acc[a], t);
-                        break;
-                    }
-                    case CSTRIPE_AGG_SUM_DISC_I64: {
-                        ov_pick<R, NS>(lo, c, sa, oa, ha);
-                        ov_pick<R, NS>(lo, c, sb, ob, hb);
-                        __int128 t = 0;
-                        #pragma unroll
-                        for (int k = 0; k < R; k++)
-                            if ((pv >> k) & 1u)
-                                t += (__int128)ov_val(oa[k], ha) * (g.one - ov_val(ob[k], hb));
-                        acc_add_i128(acc[a], t);
-                        break;
-                    }
-                    case CSTRIPE_AGG_SUM_DISC_TAX_I64: {
-                        ov_pick<R, NS>(lo, c, sa, oa, ha);
-                        ov_pick<R, NS>(lo, c, sb, ob, hb);
-                        ov_pick<R, NS>(lo, c, sc, oc, hc);
-                        __int128 t = 0;
-                        #pragma unroll
-                        for (int k = 0; k < R; k++)
-                            if ((pv >> k) & 1u)
-                                t += (__int128)ov_val(oa[k], ha) * (g.one - ov_val(ob[k], hb))
-                                     * (g.one + ov_val(oc[k], hc));
-                        acc_add_i128(acc[a], t);
-                        break;
-                    }
-                    default:
-                        break;
-                }
-                acc[a].cnt += cnt;
+            if constexpr (!WIN) {
+                #pragma unroll
+                for (int k = 0; k < R; k++) wn[s][k] = nw[s][k];
             }
         }
-
-        /* rotate the descriptor pipeline; the ColLocs fetched in (3) are
-         * first touched here, a whole fold later */
-        #pragma unroll
-        for (int s = 0; s < NS; s++) { c[s] = nc[s]; nc[s] = ov_col(nn[s]); }
         crc = nrc; crow = nrow;
+        if constexpr (!WIN) crows = nrows;
         nrc = nnrc;
         g2 = g3;
     }
 
     /* one wave/block reduce per block */
-    __shared__ ThreadAcc lds[AGG_BLOCK / WAVE][NAGGS];
-    const uint32_t wid = threadIdx.x / WAVE;
-    const uint32_t lane = threadIdx.x % WAVE;
-    #pragma unroll
-    for (int a = 0; a < NAGGS; a++) {
-        if (!EXACT && (uint32_t)a >= n_aggs) continue;
-        wave_reduce(acc[a], params.aggs[a].kind);
-        if (lane == 0) lds[wid][a] = acc[a];
-    }
-    __syncthreads();
-    if (wid == 0) {
-        for (uint32_t a = lane; a < n_aggs; a += WAVE) {
-            ThreadAcc r = lds[0][a];
-            for (uint32_t w = 1; w < AGG_BLOCK / WAVE; w++)
-                acc_merge(r, lds[w][a], params.aggs[a].kind);
-            AccCell cell;
-            cell.lo = r.lo; cell.hi = r.hi; cell.f = r.f; cell.cnt = r.cnt;
-            block_out[(uint64_t)blockIdx.x * n_aggs + a] = cell;
-        }
-    }
+    block_reduce<NAGGS, true>(acc, params, n_aggs, block_out);
 }
 
 /* per-row precomputed aggregate contribution: operands loaded ONCE per row,
@@ -2469,7 +2252,6 @@ __global__ __launch_bounds__(AGG_BLOCK, 4) void multi_grouped_kernel(
     const AggParams &params = gp.base;
     const uint32_t n_aggs = NAGGS >= 0 ? (uint32_t)NAGGS : params.n_aggs;
     const uint32_t wid = threadIdx.x / WAVE;
-    const uint32_t lane = threadIdx.x % WAVE;
     const uint32_t n_waves = AGG_BLOCK / WAVE;
     constexpr uint32_t HALF = (uint32_t)R * AGG_BLOCK;   /* rows per pass */
 
@@ -5867,30 +5649,25 @@ static int agg_ungrouped(cstripe_scan *s, const cstripe_agg_spec *aggs,
             constexpr uint32_t KSIG_Q6 = ov_ksig(0, CSTRIPE_AGG_SUM_PROD_I64) |
                                          ov_ksig(1, CSTRIPE_AGG_COUNT_STAR);
             constexpr uint32_t KSIG_CNT = ov_ksig(0, CSTRIPE_AGG_COUNT_STAR);
-            /* zstd streams (rows 1..4 bytes apart) keep the window form */
             const bool q6 = pl.n_slots == 4 && pl.n_pslots == 3 && p.n_preds == 5 &&
                             n_aggs == 2 && pl.sig == SIG_Q6 && pl.ksig == KSIG_Q6;
             const bool cnt = pl.n_slots == 1 && p.n_preds == 1 && n_aggs == 1 &&
                              pl.sig == 0 && pl.ksig == KSIG_CNT;
-            if (g->any_zr) {
+            auto launch_form = [&](auto win) {
+                constexpr bool WIN = decltype(win)::value;
                 if (q6)
-                    launcho(multi_agg_kernel_ovw<OV_R, 4, 3, 5, 2, true, OV_WAVES,
-                                                 SIG_Q6, KSIG_Q6>, OV_R);
+                    launcho(multi_agg_kernel_ov<WIN, OV_R, 4, 3, 5, 2, true, OV_WAVES,
+                                                SIG_Q6, KSIG_Q6>, OV_R);
                 else if (cnt)
-                    launcho(multi_agg_kernel_ovw<OV_R, 1, 1, 1, 1, true, OV_WAVES,
-                                                 0, KSIG_CNT>, OV_R);
+                    launcho(multi_agg_kernel_ov<WIN, OV_R, 1, 1, 1, 1, true, OV_WAVES,
+                                                0, KSIG_CNT>, OV_R);
                 else
-                    launcho(multi_agg_kernel_ovw<OV_R_ANY, OV_MAX_SLOTS, OV_MAX_SLOTS, 0,
-                                                 OV_MAX_AGGS, false, OV_WAVES>, OV_R_ANY);
-            } else if (q6)
-                launcho(multi_agg_kernel_ov<OV_R, 4, 3, 5, 2, true, OV_WAVES,
-                                            SIG_Q6, KSIG_Q6>, OV_R);
-            else if (cnt)
-                launcho(multi_agg_kernel_ov<OV_R, 1, 1, 1, 1, true, OV_WAVES,
-                                            0, KSIG_CNT>, OV_R);
-            else
-                launcho(multi_agg_kernel_ov<OV_R_ANY, OV_MAX_SLOTS, OV_MAX_SLOTS, 0,
-                                            OV_MAX_AGGS, false, OV_WAVES>, OV_R_ANY);
+                    launcho(multi_agg_kernel_ov<WIN, OV_R_ANY, OV_MAX_SLOTS, OV_MAX_SLOTS, 0,
+                                                OV_MAX_AGGS, false, OV_WAVES>, OV_R_ANY);
+            };
+            /* zstd streams (rows 1..4 bytes apart) keep the window form */
+            if (g->any_zr) launch_form(std::true_type{});
+            else launch_form(std::false_type{});
             HIP_TRY(hipGetLastError());
             { int _rc = launch_final_reduce(g, grid, p); if (_rc != CSTRIPE_OK) return _rc; }
             HIP_TRY(hipEventRecord(g->ev2, g->stream));

@@ -254,6 +254,30 @@ def test_multi_item_walk(tmp_path, cgrl, n):
     check(path, cols, *count_query(9000), want_path=PATH_OV, what="count")
 
 
+@pytest.mark.parametrize("comp", [ca.COMP_LZ4, ca.COMP_ZSTD], ids=["lz4", "zstd"])
+def test_multi_item_walk_two_tiles(tmp_path, comp):
+    """both load forms (lz4: lane-contiguous, zstd: per-lane windows) with a
+    block walking several work items, so that the words loaded one trip ahead
+    and the rotate at the loop's end are what the next trip reads: 520 chunk
+    groups of 2049 rows (two tiles at R = 8, three at R = 4, the last holding
+    one row) and a last group of 9 rows, the shortest the writer stores
+    canonically in every case. 1042 / 1563 work items against a fixed grid of
+    four blocks per CU (1024 on 256 CUs)."""
+    cg, n_full, tail = 2049, 520, 9
+    n = cg * n_full + tail
+    rng = np.random.default_rng(21)
+    cols = big_table(n, rng)
+    path = write(tmp_path / "t.cs", cols, comp=comp, chunk_group_row_limit=cg,
+                 stripe_row_limit=64 * cg)
+    assert eligible(path, [0, 1, 2, 3])
+    P = futil.SEGMODE_ZRP_BASE if comp == ca.COMP_ZSTD else futil.SEGMODE_P_BASE
+    assert {m & ~0xF for m in col_modes(path, 0)} == {P}
+    assert len(col_modes(path, 0)) == n_full + 1
+    check(path, cols, *Q6ISH, want_path=PATH_OV, what="q6")
+    check(path, cols, *any_query(8766, 9131), want_path=PATH_OV, what="any")
+    check(path, cols, *count_query(9000), want_path=PATH_OV, what="count")
+
+
 @pytest.mark.parametrize("where", ["leading", "middle", "trailing"])
 def test_pruned_groups(tmp_path, where):
     """chunk groups removed by min/max pruning before the kernel runs"""
