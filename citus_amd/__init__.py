@@ -171,6 +171,124 @@ def make_lookups(lookups):
     return arr, len(lookups)
 
 
+MAX_EXPRS = 8
+MAX_EXPR_OPS = 48
+MAX_EXPR_DEPTH = 8
+(EX_COL, EX_CONST, EX_NULL, EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD, EX_NEG,
+ EX_LT, EX_LE, EX_GT, EX_GE, EX_EQ, EX_NE, EX_AND, EX_OR, EX_NOT,
+ EX_IS_NULL, EX_COALESCE, EX_SELECT, EX_YEAR) = range(22)
+
+
+class ExprOp(C.Structure):
+    """cstripe_expr_op"""
+    _fields_ = [("op", C.c_uint32), ("column", C.c_uint32), ("ival", C.c_int64)]
+
+
+class ExprIn(C.Structure):
+    """cstripe_expr"""
+    _fields_ = [("ops", C.POINTER(ExprOp)), ("n_ops", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class Expr:
+    """A row-level int64 expression for Reader.scan(exprs=[...]), built from
+    col(i), lit(v) and null() with + - * // % and unary -, the comparisons
+    .lt/.le/.gt/.ge/.eq/.ne (0 / 1), the three-valued & | ~, .is_null(),
+    .year(), coalesce(a, b) and case(cond, then, else_). A Python int where
+    an expression is expected is a literal. `ops` is the postfix program, a
+    list of (op, column, ival) tuples; // and % follow PG int8 (truncation
+    toward zero, the dividend's sign), not Python. See
+    cstripe_scan_begin_exprs in include/cstripe.h for the value semantics."""
+
+    def __init__(self, ops):
+        self.ops = list(ops)
+
+    def _bin(self, op, other, swap=False):
+        a, b = (as_expr(other), self) if swap else (self, as_expr(other))
+        return Expr(a.ops + b.ops + [(op, 0, 0)])
+
+    def __add__(self, o): return self._bin(EX_ADD, o)
+    def __radd__(self, o): return self._bin(EX_ADD, o, True)
+    def __sub__(self, o): return self._bin(EX_SUB, o)
+    def __rsub__(self, o): return self._bin(EX_SUB, o, True)
+    def __mul__(self, o): return self._bin(EX_MUL, o)
+    def __rmul__(self, o): return self._bin(EX_MUL, o, True)
+    def __floordiv__(self, o): return self._bin(EX_DIV, o)
+    def __rfloordiv__(self, o): return self._bin(EX_DIV, o, True)
+    def __mod__(self, o): return self._bin(EX_MOD, o)
+    def __rmod__(self, o): return self._bin(EX_MOD, o, True)
+    def __and__(self, o): return self._bin(EX_AND, o)
+    def __rand__(self, o): return self._bin(EX_AND, o, True)
+    def __or__(self, o): return self._bin(EX_OR, o)
+    def __ror__(self, o): return self._bin(EX_OR, o, True)
+    def __neg__(self): return Expr(self.ops + [(EX_NEG, 0, 0)])
+    def __invert__(self): return Expr(self.ops + [(EX_NOT, 0, 0)])
+    def lt(self, o): return self._bin(EX_LT, o)
+    def le(self, o): return self._bin(EX_LE, o)
+    def gt(self, o): return self._bin(EX_GT, o)
+    def ge(self, o): return self._bin(EX_GE, o)
+    def eq(self, o): return self._bin(EX_EQ, o)
+    def ne(self, o): return self._bin(EX_NE, o)
+    def is_null(self): return Expr(self.ops + [(EX_IS_NULL, 0, 0)])
+    def year(self): return Expr(self.ops + [(EX_YEAR, 0, 0)])
+
+
+def as_expr(v):
+    """an Expr as it is; a Python / numpy int as a literal"""
+    if isinstance(v, Expr):
+        return v
+    if isinstance(v, bool) or not hasattr(v, "__index__"):
+        raise CStripeError(f"expression operand {v!r} is neither an Expr nor an int")
+    return lit(v)
+
+
+def col(i):
+    """the value of table or lookup-derived column i"""
+    return Expr([(EX_COL, int(i), 0)])
+
+
+def lit(v):
+    """the int64 constant v"""
+    v = int(v)
+    if not -(1 << 63) <= v < (1 << 63):
+        raise CStripeError(f"expression literal {v} is outside int64")
+    return Expr([(EX_CONST, 0, v)])
+
+
+def null():
+    return Expr([(EX_NULL, 0, 0)])
+
+
+def coalesce(a, b):
+    """a unless it is NULL, then b"""
+    return Expr(as_expr(a).ops + as_expr(b).ops + [(EX_COALESCE, 0, 0)])
+
+
+def case(cond, then, else_=None):
+    """CASE WHEN cond THEN then ELSE else_ END; else_ defaults to NULL"""
+    e = null() if else_ is None else as_expr(else_)
+    return Expr(as_expr(cond).ops + as_expr(then).ops + e.ops + [(EX_SELECT, 0, 0)])
+
+
+def make_exprs(exprs):
+    """(ExprIn array or None, n) for cstripe_scan_begin_exprs from Expr
+    objects, ints, or raw lists of (op, column, ival) tuples; the array keeps
+    the op arrays it points at alive"""
+    if not exprs:
+        return None, 0
+    arr = (ExprIn * len(exprs))()
+    keep = []
+    for i, ex in enumerate(exprs):
+        ops = list(ex) if isinstance(ex, (list, tuple)) else as_expr(ex).ops
+        oa = (ExprOp * max(1, len(ops)))()
+        for k, (op, column, ival) in enumerate(ops):
+            oa[k].op, oa[k].column, oa[k].ival = int(op), int(column), int(ival)
+        arr[i].ops = C.cast(oa, C.POINTER(ExprOp))
+        arr[i].n_ops = len(ops)
+        keep.append(oa)
+    arr._keep = keep
+    return arr, len(exprs)
+
+
 class AggSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("col_a", C.c_int32), ("col_b", C.c_int32),
                 ("col_c", C.c_int32), ("one", C.c_int64)]
@@ -312,6 +430,17 @@ _scan_begin_lookups = _sig("cstripe_scan_begin_lookups", C.c_void_p,
                             C.POINTER(TextConst), C.c_uint32,
                             C.POINTER(ValueSet), C.c_uint32,
                             C.POINTER(LookupIn), C.c_uint32])
+_scan_begin_exprs = _sig("cstripe_scan_begin_exprs", C.c_void_p,
+                         [C.c_void_p, C.c_uint64, C.POINTER(Pred), C.c_uint32,
+                          C.POINTER(TextConst), C.c_uint32,
+                          C.POINTER(ValueSet), C.c_uint32,
+                          C.POINTER(LookupIn), C.c_uint32,
+                          C.POINTER(ExprIn), C.c_uint32])
+_expr_range = _sig("cstripe_scan_expr_range", C.c_int,
+                   [C.c_void_p, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                    C.POINTER(C.c_uint64)])
+_last_expr_ms = _sig("cstripe_scan_last_expr_ms", C.c_int,
+                     [C.c_void_p, C.POINTER(C.c_double)])
 _scan_column_count = _sig("cstripe_scan_column_count", C.c_uint32, [C.c_void_p])
 _last_lookup_ms = _sig("cstripe_scan_last_lookup_ms", C.c_int,
                        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)])
@@ -659,10 +788,12 @@ class Reader:
         _check(_column_def(self._h, i, C.byref(d)), "column_def")
         return d.name.decode(), d.type, d.scale
 
-    def scan(self, cols_mask=0, preds=(), lookups=()):
+    def scan(self, cols_mask=0, preds=(), lookups=(), exprs=()):
         """lookups: a list of Lookup — each payload becomes a derived int64
-        column with id column_count + ..., see Scan.derived()"""
-        return Scan(self, cols_mask, preds, lookups)
+        column with id column_count + ..., see Scan.derived(). exprs: a list
+        of Expr (or raw postfix lists) — each becomes a computed int64 column
+        after the derived ones, see Scan.computed()"""
+        return Scan(self, cols_mask, preds, lookups, exprs)
 
 
 def make_preds(preds):
@@ -1094,11 +1225,20 @@ def merge_topn(results, order, limit, offset=0, text=False):
 
 
 class Scan:
-    def __init__(self, reader, cols_mask, preds, lookups=()):
+    def __init__(self, reader, cols_mask, preds, lookups=(), exprs=()):
         self._sets = None
         self._lookups = None
         self._lookup_payloads = [len(lk.payloads) for lk in lookups]
-        if lookups:                               # N:1 joins: derived columns
+        self._exprs = None
+        self._n_exprs = len(exprs)
+        if exprs:                                 # expressions: computed columns
+            self._preds, self._texts, n_texts, self._sets, n_sets = make_preds_sets(preds)
+            self._lookups, n_lk = make_lookups(list(lookups))
+            self._exprs, n_ex = make_exprs(list(exprs))
+            self._h = _scan_begin_exprs(reader._h, cols_mask, self._preds, len(preds),
+                                        self._texts, n_texts, self._sets, n_sets,
+                                        self._lookups, n_lk, self._exprs, n_ex)
+        elif lookups:                             # N:1 joins: derived columns
             self._preds, self._texts, n_texts, self._sets, n_sets = make_preds_sets(preds)
             self._lookups, n_lk = make_lookups(list(lookups))
             self._h = _scan_begin_lookups(reader._h, cols_mask, self._preds, len(preds),
@@ -1127,10 +1267,16 @@ class Scan:
                 self._mask |= 1 << p[0]
         for lk in lookups:
             self._mask |= 1 << lk.key_col        # key columns are read too
+        # and an expression's table inputs
+        for i in range(self._n_exprs):
+            for k in range(self._exprs[i].n_ops):
+                op = self._exprs[i].ops[k]
+                if op.op == EX_COL and op.column < ntab:
+                    self._mask |= 1 << op.column
         if self._mask == 0:
             self._mask = 1
-        # derived columns are always projected
-        for c in range(ntab, ntab + sum(self._lookup_payloads)):
+        # derived and computed columns are always projected
+        for c in range(ntab, ntab + sum(self._lookup_payloads) + self._n_exprs):
             self._mask |= 1 << c
         self._device = -1
 
@@ -1220,7 +1366,7 @@ class Scan:
         return rc, size.value
 
     def column_count(self):
-        """table columns + derived (lookup payload) columns of this scan
+        """table + derived (lookup payload) + computed (expression) columns of this scan
         (cstripe_scan_column_count). A method, as the C entry is a call on
         the scan — unlike the Reader.column_count property, which it equals
         for a scan without lookups."""
@@ -1231,6 +1377,27 @@ class Scan:
         if not (0 <= l < len(self._lookup_payloads) and 0 <= p < self._lookup_payloads[l]):
             raise CStripeError(f"derived: no payload {p} of lookup {l} in this scan")
         return self._reader.column_count + sum(self._lookup_payloads[:l]) + p
+
+    def computed(self, e):
+        """column id of expression e"""
+        if not 0 <= e < self._n_exprs:
+            raise CStripeError(f"computed: no expression {e} in this scan")
+        return self._reader.column_count + sum(self._lookup_payloads) + e
+
+    def expr_range(self, e):
+        """(lo, hi, n_present) of computed column e over the selected chunk
+        groups, measured by the last stage(); an all-NULL column gives
+        (0, 0, 0)"""
+        lo, hi, n = C.c_int64(), C.c_int64(), C.c_uint64()
+        _check(_expr_range(self._h, e, C.byref(lo), C.byref(hi), C.byref(n)), "scan_expr_range")
+        return lo.value, hi.value, n.value
+
+    def last_expr_ms(self):
+        """device ms of the last stage()'s expression evaluation launches,
+        all expressions together; 0 without one"""
+        ms = C.c_double()
+        _check(_last_expr_ms(self._h, C.byref(ms)), "scan_last_expr_ms")
+        return ms.value
 
     def last_lookup_ms(self):
         """(build, probe) device ms of the last stage()'s lookup work, all
@@ -1250,7 +1417,7 @@ class Scan:
         return rc, size.value
 
     def _col_type(self, c):
-        """cstripe type of a table or derived (I64) column id"""
+        """cstripe type of a table or derived / computed (I64) column id"""
         ntab = self._reader.column_count
         return I64 if c >= ntab else self._reader.column_def(c)[1]
 

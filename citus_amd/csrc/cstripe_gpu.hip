@@ -230,6 +230,9 @@ struct cs_gpu_state {
      * after the member slots) per payload; proj_of_col covers their ids */
     struct DerivedSlot { uint32_t lookup, payload, proj; };
     std::vector<DerivedSlot> dslots;
+    /* expressions: one computed slot (a projected sparse I64 column in
+     * scratch, after the derived slots) per expression */
+    std::vector<uint32_t> eslots;    /* [expression] -> projected slot */
 };
 
 /* ---------------- error helper ---------------- */
@@ -3400,6 +3403,7 @@ void csgpu_release(cstripe_scan *s)
     s->gpu = nullptr;
     for (cs_value_set &vs : s->sets) { vs.form = 0; vs.form_size = 0; }
     for (cs_lookup &lk : s->lookups) { lk.form = 0; lk.form_size = 0; }
+    for (cs_expr &ex : s->exprs) { ex.lo = ex.hi = 0; ex.n_present = 0; }
 }
 
 uint64_t csgpu_staged_bytes(const cstripe_scan *s)
@@ -3437,6 +3441,7 @@ struct VtTemps {
 static int vartext_build(cstripe_scan *s, VtTemps &vt);
 static int sets_build(cstripe_scan *s, VtTemps &st);
 static int lookups_build(cstripe_scan *s, VtTemps &lt);
+static int exprs_build(cstripe_scan *s, VtTemps &et);
 
 int csgpu_stage(cstripe_scan *s, int device_id)
 {
@@ -3506,6 +3511,21 @@ int csgpu_stage(cstripe_scan *s, int device_id)
             n_proj++;
         }
     if (!g->dslots.empty()) { g->fusable = false; g->all_dense = false; }
+    /* computed slots of the expressions, after the derived slots */
+    for (size_t e = 0; e < s->exprs.size(); e++) {
+        if (n_proj >= MAX_PROJ) {
+            cs_set_err("gpu_stage: %u projected columns plus the computed columns of the "
+                       "expressions exceed the %d slots of one scan (expression %u)",
+                       n_proj, MAX_PROJ, (unsigned)e);
+            csgpu_release(s);
+            return CSTRIPE_ERR_ARG;
+        }
+        g->eslots.push_back(n_proj);
+        g->proj_of_col[s->exprs[e].first_col] = (int)n_proj;
+        g->proj_type[n_proj] = CSTRIPE_I64;
+        n_proj++;
+    }
+    if (!g->eslots.empty()) { g->fusable = false; g->all_dense = false; }
     g->n_proj = n_proj;
     g->n_groups = (uint32_t)s->sel.size();
 
@@ -3575,9 +3595,18 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 scratch_bytes = align_up(scratch_bytes, 16) +
                                 align_up((uint64_t)st.nodes[lk.key_column][sc.chunk].n.n_present * 8, 16);
         }
+        /* computed columns: per expression a device-written exists bitmap
+         * and rank table and room for one value per ROW (the result's NULL
+         * count is not known in advance), in a scratch region no decode
+         * segment writes */
+        for (size_t e = 0; e < g->eslots.size(); e++) {
+            data_bytes = align_up(data_bytes, 8) + align_up((rows + 7) / 8, 8);
+            rank_words += (rows + 63) / 64;
+            scratch_bytes = align_up(scratch_bytes, 16) + align_up((uint64_t)rows * 8, 16);
+        }
     }
     (void)zstd_host;
-    if (any_vartext || !g->mslots.empty() || !g->dslots.empty())
+    if (any_vartext || !g->mslots.empty() || !g->dslots.empty() || !g->eslots.empty())
         scratch_bytes += 64;        /* the R-row windowed loads of the dense
                                      * kernels reach up to R-1 entries past a
                                      * rank array's end */
@@ -3872,15 +3901,35 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 h_colloc[(uint64_t)gi * n_proj + g->dslots[ds].proj] = cl;
             }
         }
+        for (size_t e = 0; e < g->eslots.size(); e++) {
+            /* a computed column reads as a sparse I64 column in scratch, laid
+             * out like a derived one; expr_eval_kernel writes its bitmap
+             * (zero here), rank words and values (exprs_build) */
+            ColLoc cl{};
+            cl.type = CSTRIPE_I64;
+            cl.width = 8;
+            cl.flags = 1;
+            dpos = align_up(dpos, 8);
+            cl.exists_off = dpos;
+            dpos += align_up((rows + 7) / 8, 8);
+            cl.rank_off = (uint32_t)h_rank.size();
+            h_rank.resize(h_rank.size() + (rows + 63) / 64, 0);
+            spos = align_up(spos, 16);
+            cl.val_off = spos;
+            spos += align_up((uint64_t)rows * 8, 16);
+            h_colloc[(uint64_t)gi * n_proj + g->eslots[e]] = cl;
+        }
     }
 
     /* invariant: the layout pass and the fill pass must agree exactly —
      * any drift between them is silent corruption (heap overflow on the
      * host copy or device reads past staged regions) */
-    if (align_up(dpos, 16) > data_bytes || align_up(spos, 16) > scratch_bytes + 15) {
-        cs_set_err("staging layout drift: filled %llu/%llu data, %llu/%llu scratch",
+    if (align_up(dpos, 16) > data_bytes || align_up(spos, 16) > scratch_bytes + 15 ||
+        h_rank.size() > rank_words) {
+        cs_set_err("staging layout drift: filled %llu/%llu data, %llu/%llu scratch, %llu/%llu rank words",
                    (unsigned long long)dpos, (unsigned long long)data_bytes,
-                   (unsigned long long)spos, (unsigned long long)scratch_bytes);
+                   (unsigned long long)spos, (unsigned long long)scratch_bytes,
+                   (unsigned long long)h_rank.size(), (unsigned long long)rank_words);
         csgpu_release(s);
         return CSTRIPE_ERR;
     }
@@ -3985,6 +4034,17 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         VtTemps lt;
         int rc = lookups_build(s, lt);
         lt.release();
+        if (rc != CSTRIPE_OK) {
+            csgpu_release(s);
+            s->text_dicts.clear();
+            return rc;
+        }
+    }
+    s->last_expr_ms = 0;
+    if (!g->eslots.empty()) {
+        VtTemps et;
+        int rc = exprs_build(s, et);
+        et.release();
         if (rc != CSTRIPE_OK) {
             csgpu_release(s);
             s->text_dicts.clear();
@@ -5354,6 +5414,335 @@ static int lookups_build(cstripe_scan *s, VtTemps &lt)
     return CSTRIPE_OK;
 }
 
+/* =====================================================================
+ * Expressions — device-computed columns.
+ *
+ * No query kernel knows about expressions. At stage each expression becomes
+ * a COMPUTED column: a sparse I64 column in scratch, laid out like a lookup's
+ * derived column, whose exists bitmap, rank table and compacted values are
+ * written by ONE kernel, expr_eval_kernel: one launch per expression, one
+ * block per chunk group. The block walks its group in tiles of AGG_BLOCK
+ * rows carrying a running base; each lane reads its row's inputs through
+ * col_value (any stream shape), runs the postfix program, and the wave
+ * ballots the non-NULL bit: lane 0 stores the exists word and the rank word
+ * (running base + the waves before it, four wave totals through LDS), every
+ * non-NULL lane its value at rank + popc(bits below). No per-row temporary,
+ * no second pass. Lanes past the group's rows are NULL, so a partial last
+ * word has zero high bits.
+ *
+ * The program travels by value in the kernel arguments and is wave-uniform:
+ * the interpreter's switch does not diverge. The operand stack lives in LDS,
+ * laid out [depth][thread] (a lane's entries sit AGG_BLOCK slots apart, so a
+ * wave's access is one contiguous row: no bank conflicts), never in private
+ * memory. Each entry is a value plus a flag byte: bit 0 NULL, bits 1..2 the
+ * error code; the semantics are those of include/cstripe.h.
+ * ===================================================================== */
+
+#define EX_F_NULL  1u
+#define EX_E_DIV0  1u       /* error codes, in flag bits 1..2 */
+#define EX_E_RANGE 2u
+#define EX_E_YEAR  3u
+
+struct ExprProg {
+    int64_t ival[CSTRIPE_MAX_EXPR_OPS];
+    uint8_t op[CSTRIPE_MAX_EXPR_OPS];
+    uint8_t proj[CSTRIPE_MAX_EXPR_OPS];   /* EX_COL: projected slot of the input */
+    uint32_t n_ops;
+    uint32_t pad;
+};
+static_assert(sizeof(ExprProg) <= 768, "the program travels in the kernel arguments");
+
+/* per expression: range and count of the non-NULL results, and per error
+ * kind the first row in scan order (group << 32 | row) whose final value
+ * carries it, ~0 when none */
+struct ExprState {
+    long long mn, mx;
+    unsigned long long cnt;
+    unsigned long long err_row[3];
+};
+
+/* proleptic Gregorian (astronomical) year of a day count from 1970-01-01 */
+__device__ inline int64_t expr_year(int64_t days)
+{
+    const int64_t z = days + 719468;
+    const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
+    const int64_t doe = z - era * 146097;
+    const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+    const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+    const int64_t mp = (5 * doy + 2) / 153;
+    return yoe + era * 400 + (mp >= 10 ? 1 : 0);   /* January, February: next year of the March-based count */
+}
+
+/* writes only the computed column's own regions: the exists words
+ * (rows + 63) / 64 (8-byte padded at layout), as many rank words, and value
+ * indexes below the group's rows, which sized the value region */
+__global__ __launch_bounds__(AGG_BLOCK) void expr_eval_kernel(
+    uint8_t *data, uint8_t *scratch, uint32_t *rank,
+    const GroupDesc *__restrict__ groups, const ColLoc *__restrict__ colloc,
+    uint32_t n_proj, uint32_t e_proj, ExprState *state, ExprProg pg)
+{
+    __shared__ int64_t sv[CSTRIPE_MAX_EXPR_DEPTH][AGG_BLOCK];
+    __shared__ uint8_t sf[CSTRIPE_MAX_EXPR_DEPTH][AGG_BLOCK];
+    __shared__ uint32_t wsum[LK_WAVES];
+    __shared__ long long rmn[LK_WAVES], rmx[LK_WAVES];
+    __shared__ uint32_t rcnt[LK_WAVES];
+    const uint32_t gi = blockIdx.x;
+    const uint32_t rows = groups[gi].row_count;
+    const ColLoc *cls = colloc + (uint64_t)gi * n_proj;
+    uint64_t *bm = (uint64_t *)(data + cls[e_proj].exists_off);
+    uint32_t *rk = rank + cls[e_proj].rank_off;
+    int64_t *vals = (int64_t *)(scratch + cls[e_proj].val_off);
+    const uint32_t t = threadIdx.x, lane = t % WAVE, wave = t / WAVE;
+    uint32_t base = 0, cnt = 0;
+    long long mn = INT64_MAX, mx = INT64_MIN;
+    for (uint32_t r0 = 0; r0 < rows; r0 += AGG_BLOCK) {
+        const uint32_t row = r0 + t;
+        const bool live = row < rows;
+        uint32_t sp = 0;
+        for (uint32_t i = 0; i < pg.n_ops; i++) {
+            const uint32_t op = pg.op[i];
+            int64_t v = 0;
+            uint32_t f = 0;
+            switch (op) {
+                case CSTRIPE_EX_COL: {
+                    double fv = 0;
+                    f = EX_F_NULL;
+                    if (live && col_value(data, scratch, rank, cls[pg.proj[i]], row, v, fv)) f = 0;
+                    break;
+                }
+                case CSTRIPE_EX_CONST:
+                    v = pg.ival[i];
+                    break;
+                case CSTRIPE_EX_NULL:
+                    f = EX_F_NULL;
+                    break;
+                case CSTRIPE_EX_NEG: case CSTRIPE_EX_NOT: case CSTRIPE_EX_IS_NULL: case CSTRIPE_EX_YEAR: {
+                    const int64_t a = sv[sp - 1][t];
+                    const uint32_t fa = sf[sp - 1][t];
+                    sp -= 1;
+                    uint32_t err = fa >> 1;
+                    if (op == CSTRIPE_EX_IS_NULL) {
+                        v = fa & EX_F_NULL;
+                    } else if (fa & EX_F_NULL) {
+                        f = EX_F_NULL;
+                    } else if (!err) {
+                        if (op == CSTRIPE_EX_NOT) v = a == 0;
+                        else if (op == CSTRIPE_EX_NEG) { if (__builtin_sub_overflow((int64_t)0, a, &v)) err = EX_E_RANGE; }
+                        else if (a < -(1ll << 31) || a >= (1ll << 31)) err = EX_E_YEAR;
+                        else v = expr_year(a);
+                    }
+                    f |= err << 1;
+                    break;
+                }
+                case CSTRIPE_EX_AND: case CSTRIPE_EX_OR: {
+                    /* Kleene, left to right: a clean left operand that decides
+                     * (FALSE for AND, TRUE for OR) hides the right one */
+                    const int64_t b = sv[sp - 1][t], a = sv[sp - 2][t];
+                    const uint32_t fb = sf[sp - 1][t], fa = sf[sp - 2][t];
+                    sp -= 2;
+                    const int64_t decides = op == CSTRIPE_EX_AND ? 0 : 1;
+                    if (fa >> 1) {
+                        f = fa & ~EX_F_NULL;
+                    } else if (!(fa & EX_F_NULL) && (a != 0) == decides) {
+                        v = decides;
+                    } else if (fb >> 1) {
+                        f = fb & ~EX_F_NULL;
+                    } else if (!(fb & EX_F_NULL) && (b != 0) == decides) {
+                        v = decides;
+                    } else if ((fa | fb) & EX_F_NULL) {
+                        f = EX_F_NULL;
+                    } else {
+                        v = 1 - decides;
+                    }
+                    break;
+                }
+                case CSTRIPE_EX_COALESCE: {
+                    const int64_t b = sv[sp - 1][t], a = sv[sp - 2][t];
+                    const uint32_t fb = sf[sp - 1][t], fa = sf[sp - 2][t];
+                    sp -= 2;
+                    const bool take_a = (fa >> 1) || !(fa & EX_F_NULL);
+                    v = take_a ? a : b;
+                    f = take_a ? fa : fb;
+                    break;
+                }
+                case CSTRIPE_EX_SELECT: {
+                    const int64_t b = sv[sp - 1][t], a = sv[sp - 2][t], c = sv[sp - 3][t];
+                    const uint32_t fb = sf[sp - 1][t], fa = sf[sp - 2][t], fc = sf[sp - 3][t];
+                    sp -= 3;
+                    if (fc >> 1) {
+                        f = fc & ~EX_F_NULL;
+                    } else {
+                        const bool then = !(fc & EX_F_NULL) && c != 0;
+                        v = then ? a : b;
+                        f = then ? fa : fb;
+                    }
+                    break;
+                }
+                default: {
+                    /* strict binary ops: the left operand's error, else the
+                     * right one's, else NULL, else the op itself */
+                    const int64_t b = sv[sp - 1][t], a = sv[sp - 2][t];
+                    const uint32_t fb = sf[sp - 1][t], fa = sf[sp - 2][t];
+                    sp -= 2;
+                    uint32_t err = (fa >> 1) ? (fa >> 1) : (fb >> 1);
+                    f = (fa | fb) & EX_F_NULL;
+                    if (!f && !err) {
+                        switch (op) {
+                            case CSTRIPE_EX_ADD: if (__builtin_add_overflow(a, b, &v)) err = EX_E_RANGE; break;
+                            case CSTRIPE_EX_SUB: if (__builtin_sub_overflow(a, b, &v)) err = EX_E_RANGE; break;
+                            case CSTRIPE_EX_MUL: if (__builtin_mul_overflow(a, b, &v)) err = EX_E_RANGE; break;
+                            case CSTRIPE_EX_DIV:
+                                if (b == 0) err = EX_E_DIV0;
+                                else if (b == -1) { if (__builtin_sub_overflow((int64_t)0, a, &v)) err = EX_E_RANGE; }
+                                else v = a / b;
+                                break;
+                            case CSTRIPE_EX_MOD:
+                                if (b == 0) err = EX_E_DIV0;
+                                else if (b != -1) v = a % b;
+                                break;
+                            case CSTRIPE_EX_LT: v = a < b; break;
+                            case CSTRIPE_EX_LE: v = a <= b; break;
+                            case CSTRIPE_EX_GT: v = a > b; break;
+                            case CSTRIPE_EX_GE: v = a >= b; break;
+                            case CSTRIPE_EX_EQ: v = a == b; break;
+                            default:            v = a != b; break;
+                        }
+                        if (err) v = 0;
+                    }
+                    f |= err << 1;
+                    break;
+                }
+            }
+            sv[sp][t] = v;
+            sf[sp][t] = (uint8_t)f;
+            sp++;
+        }
+        const int64_t v = sv[0][t];
+        const uint32_t f = sf[0][t];
+        if (live && (f >> 1))
+            atomicMin(&state->err_row[(f >> 1) - 1], ((unsigned long long)gi << 32) | row);
+        const bool present = live && f == 0;
+        const uint64_t word = __ballot(present);
+        if (lane == 0) wsum[wave] = (uint32_t)__popcll(word);
+        __syncthreads();
+        uint32_t pre = 0, tot = 0;
+        for (uint32_t k = 0; k < LK_WAVES; k++) {
+            if (k < wave) pre += wsum[k];
+            tot += wsum[k];
+        }
+        const uint32_t w = (r0 >> 6) + wave;
+        if (lane == 0 && (uint64_t)w * WAVE < rows) {
+            bm[w] = word;
+            rk[w] = base + pre;
+        }
+        if (present) {
+            vals[base + pre + (uint32_t)__popcll(word & ((1ull << lane) - 1))] = v;
+            mn = v < mn ? v : mn;
+            mx = v > mx ? v : mx;
+            cnt++;
+        }
+        base += tot;
+        __syncthreads();
+    }
+    /* range and count: wave reduce, then one atomic of each per block */
+    for (uint32_t off = WAVE / 2; off; off >>= 1) {
+        const long long omn = __shfl_xor(mn, off, WAVE), omx = __shfl_xor(mx, off, WAVE);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+        cnt += __shfl_xor(cnt, off, WAVE);
+    }
+    if (lane == 0) { rmn[wave] = mn; rmx[wave] = mx; rcnt[wave] = cnt; }
+    __syncthreads();
+    if (t == 0) {
+        for (uint32_t k = 1; k < LK_WAVES; k++) {
+            mn = rmn[k] < mn ? rmn[k] : mn;
+            mx = rmx[k] > mx ? rmx[k] : mx;
+            cnt += rcnt[k];
+        }
+        if (cnt) {
+            atomicMin(&state->mn, mn);
+            atomicMax(&state->mx, mx);
+            atomicAdd(&state->cnt, (unsigned long long)cnt);
+        }
+    }
+}
+
+static const char *const expr_err_text[3] = {"division by zero", "bigint out of range", "year out of range"};
+
+static int exprs_build(cstripe_scan *s, VtTemps &et)
+{
+    cs_gpu_state *g = s->gpu;
+    const uint32_t n_proj = g->n_proj;
+    const size_t n_exprs = s->exprs.size();
+    for (hipEvent_t &e : et.ev) HIP_TRY(hipEventCreate(&e));
+
+    /* the input columns must be readable: decode what lands in scratch (as
+     * lookups_build does; the computed regions survive later decodes for the
+     * same reason the derived regions do) */
+    bool need_decode = false;
+    for (const cs_expr &ex : s->exprs)
+        for (const cstripe_expr_op &op : ex.ops)
+            if (op.op == CSTRIPE_EX_COL && g->col_scratch[(size_t)g->proj_of_col[op.column]]) need_decode = true;
+    if (need_decode && g->n_groups) {
+        HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
+        { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
+        int h_err = 0;
+        HIP_TRY(hipMemcpyAsync(&h_err, g->d_error, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (h_err) { cs_set_err("decode error on device (flag %d)", h_err); return CSTRIPE_ERR_FORMAT; }
+    }
+
+    std::vector<ExprState> h_state(n_exprs);
+    for (ExprState &st : h_state) {
+        st.mn = INT64_MAX;
+        st.mx = INT64_MIN;
+        st.cnt = 0;
+        st.err_row[0] = st.err_row[1] = st.err_row[2] = ~0ull;
+    }
+    ExprState *d_state = nullptr;
+    HIP_TRY(et.alloc(d_state, n_exprs * sizeof(ExprState)));
+    HIP_TRY(hipMemcpyAsync(d_state, h_state.data(), n_exprs * sizeof(ExprState), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipEventRecord(et.ev[0], g->stream));
+    for (size_t e = 0; e < n_exprs && g->n_groups; e++) {
+        const cs_expr &ex = s->exprs[e];
+        ExprProg pg{};
+        pg.n_ops = (uint32_t)ex.ops.size();
+        for (uint32_t i = 0; i < pg.n_ops; i++) {
+            pg.op[i] = (uint8_t)ex.ops[i].op;
+            pg.ival[i] = ex.ops[i].ival;
+            if (ex.ops[i].op == CSTRIPE_EX_COL) pg.proj[i] = (uint8_t)g->proj_of_col[ex.ops[i].column];
+        }
+        hipLaunchKernelGGL(expr_eval_kernel, dim3(g->n_groups), dim3(AGG_BLOCK), 0, g->stream,
+                           g->d_data, g->d_scratch, g->d_rank, g->d_groups, g->d_colloc,
+                           n_proj, g->eslots[e], d_state + e, pg);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(et.ev[1], g->stream));
+    HIP_TRY(hipMemcpyAsync(h_state.data(), d_state, n_exprs * sizeof(ExprState), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    float ms_f = 0;
+    (void)hipEventElapsedTime(&ms_f, et.ev[0], et.ev[1]);
+    s->last_expr_ms = ms_f;
+    for (size_t e = 0; e < n_exprs; e++) {
+        /* like PG, the error of the first row in scan order that has one */
+        const ExprState &st = h_state[e];
+        int kind = -1;
+        for (int k = 0; k < 3; k++)
+            if (st.err_row[k] != ~0ull && (kind < 0 || st.err_row[k] < st.err_row[kind])) kind = k;
+        if (kind >= 0) {
+            cs_set_err("gpu_stage: expression %u: %s", (unsigned)e, expr_err_text[kind]);
+            return CSTRIPE_ERR_ARG;
+        }
+    }
+    for (size_t e = 0; e < n_exprs; e++) {
+        cs_expr &ex = s->exprs[e];
+        ex.n_present = h_state[e].cnt;
+        ex.lo = ex.n_present ? h_state[e].mn : 0;
+        ex.hi = ex.n_present ? h_state[e].mx : 0;
+    }
+    return CSTRIPE_OK;
+}
+
 /* true when the spec reads a VARTEXT column as a value: its ranks are a
  * per-scan coding, so only COUNT_COL (presence) means anything */
 static bool agg_reads_vartext(const cstripe_reader *r, const cstripe_agg_spec &a)
@@ -5768,7 +6157,7 @@ static int agg_grouped(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t n
     for (uint32_t i = 0; i < n_group_cols; i++) {
         int pj = proj_of(s, (int32_t)group_cols[i]);
         if (pj < 0) { cs_set_err("group col %u not projected", group_cols[i]); return CSTRIPE_ERR_ARG; }
-        if (cs_col_derived(s, group_cols[i])) { cs_set_err("group col %u is a derived (lookup) column: scan_agg_grouped takes I8 or TEXT table columns; use scan_agg_hashed", group_cols[i]); return CSTRIPE_ERR_ARG; }
+        if (cs_col_derived(s, group_cols[i])) { cs_set_err("group col %u is a derived (lookup) or computed (expression) column: scan_agg_grouped takes I8 or TEXT table columns; use scan_agg_hashed", group_cols[i]); return CSTRIPE_ERR_ARG; }
         if (r->cols[group_cols[i]].type != CSTRIPE_I8 &&
             r->cols[group_cols[i]].type != CSTRIPE_TEXT) { cs_set_err("group col %u must be I8 or TEXT", group_cols[i]); return CSTRIPE_ERR_ARG; }
         gp.gproj[i] = (uint32_t)pj;
@@ -6887,6 +7276,11 @@ static int hash_prepare(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t 
             full = true;
             tlo = lk->n ? lk->plo[pl] : 0;
             thi = lk->n ? lk->phi[pl] : 0;
+        } else if (const cs_expr *ex = cs_col_expr(s, col)) {
+            /* a computed column: the [min, max] its evaluation measured */
+            full = true;
+            tlo = ex->lo;
+            thi = ex->hi;
         } else
         for (const cs_selchunk &sc : s->sel) {
             const csf_skipnode &nd = r->stripes[sc.stripe].nodes[col][sc.chunk].n;
@@ -7595,6 +7989,10 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
             /* a derived column: the [min, max] of its payload array */
             olo = ord_i(lk->n ? lk->plo[pl] : 0);
             ohi = ord_i(lk->n ? lk->phi[pl] : 0);
+        } else if (const cs_expr *ex = cs_col_expr(s, col)) {
+            /* a computed column: the [min, max] its evaluation measured */
+            olo = ord_i(ex->lo);
+            ohi = ord_i(ex->hi);
         } else if (t == CSTRIPE_VARTEXT) {
             /* dictionary ranks: exactly [0, n_dict - 1] */
             const int64_t nd = (int64_t)s->text_dicts[col].offsets.size() - 1;

@@ -1445,12 +1445,108 @@ extern "C" cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t 
                                                     const cstripe_value_set *sets, uint32_t n_sets,
                                                     const cstripe_lookup *lookups, uint32_t n_lookups)
 {
+    return cstripe_scan_begin_exprs(r, cols_mask, preds, n_preds, text_consts, n_text_consts,
+                                    sets, n_sets, lookups, n_lookups, nullptr, 0);
+}
+
+/* validate and copy the expressions of a scan, after lookups_begin (their
+ * derived columns are legal inputs): one pass per program that simulates the
+ * stack depth; false with the message set */
+static bool exprs_begin(cstripe_scan *s, const cstripe_expr *exprs, uint32_t n_exprs)
+{
+    cstripe_reader *r = s->r;
+    if (n_exprs > CSTRIPE_MAX_EXPRS) { cs_set_err("scan_begin_exprs: %u expressions (max %d)", n_exprs, CSTRIPE_MAX_EXPRS); return false; }
+    if (n_exprs && !exprs) { cs_set_err("scan_begin_exprs: %u expressions but no array", n_exprs); return false; }
+    const uint32_t first = r->head.column_count + s->n_derived;
+    if (first + n_exprs > 64) {
+        cs_set_err("scan_begin_exprs: %u table plus %u derived plus %u computed columns exceed 64",
+                   r->head.column_count, s->n_derived, n_exprs);
+        return false;
+    }
+    std::vector<cs_expr> out(n_exprs);
+    for (uint32_t e = 0; e < n_exprs; e++) {
+        const cstripe_expr &in = exprs[e];
+        if (in.n_ops == 0 || in.n_ops > CSTRIPE_MAX_EXPR_OPS || !in.ops) {
+            cs_set_err("scan_begin_exprs: expression %u has %u ops (1..%d)", e, in.n_ops, CSTRIPE_MAX_EXPR_OPS);
+            return false;
+        }
+        uint32_t depth = 0;
+        for (uint32_t i = 0; i < in.n_ops; i++) {
+            const cstripe_expr_op &op = in.ops[i];
+            uint32_t pops;
+            switch (op.op) {
+                case CSTRIPE_EX_COL: case CSTRIPE_EX_CONST: case CSTRIPE_EX_NULL:
+                    pops = 0; break;
+                case CSTRIPE_EX_NEG: case CSTRIPE_EX_NOT: case CSTRIPE_EX_IS_NULL: case CSTRIPE_EX_YEAR:
+                    pops = 1; break;
+                case CSTRIPE_EX_SELECT:
+                    pops = 3; break;
+                default:
+                    if (op.op > CSTRIPE_EX_YEAR) {
+                        cs_set_err("scan_begin_exprs: expression %u op %u: unknown op %u", e, i, op.op);
+                        return false;
+                    }
+                    pops = 2; break;
+            }
+            if (op.op == CSTRIPE_EX_COL) {
+                if (op.column >= first) {
+                    cs_set_err("scan_begin_exprs: expression %u op %u: column %u %s", e, i, op.column,
+                               op.column < first + n_exprs
+                                   ? "is a computed column (expressions do not chain; nest SELECT)"
+                                   : "out of range");
+                    return false;
+                }
+                const uint8_t t = cs_col_type(s, op.column);
+                if (t != CSTRIPE_I8 && t != CSTRIPE_I16 && t != CSTRIPE_I32 && t != CSTRIPE_I64) {
+                    cs_set_err("scan_begin_exprs: expression %u op %u: column %u must be I8/I16/I32/I64 "
+                               "or a lookup-derived column", e, i, op.column);
+                    return false;
+                }
+            }
+            if (depth < pops) {
+                cs_set_err("scan_begin_exprs: expression %u op %u: stack underflow (op %u needs %u operands, %u on the stack)",
+                           e, i, op.op, pops, depth);
+                return false;
+            }
+            depth = depth - pops + 1;
+            if (depth > CSTRIPE_MAX_EXPR_DEPTH) {
+                cs_set_err("scan_begin_exprs: expression %u op %u: stack depth %u above the limit %d",
+                           e, i, depth, CSTRIPE_MAX_EXPR_DEPTH);
+                return false;
+            }
+        }
+        if (depth != 1) {
+            cs_set_err("scan_begin_exprs: expression %u op %u: the program leaves %u values on the stack, not 1",
+                       e, in.n_ops - 1, depth);
+            return false;
+        }
+        out[e].ops.assign(in.ops, in.ops + in.n_ops);
+        out[e].first_col = first + e;
+    }
+    s->exprs = std::move(out);
+    /* input columns are read (a derived input has no cols_mask bit) */
+    for (const cs_expr &ex : s->exprs)
+        for (const cstripe_expr_op &op : ex.ops)
+            if (op.op == CSTRIPE_EX_COL && op.column < r->head.column_count)
+                s->cols_mask |= 1ull << op.column;
+    return true;
+}
+
+extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t cols_mask,
+                                                  const cstripe_pred *preds, uint32_t n_preds,
+                                                  const cstripe_text_const *text_consts,
+                                                  uint32_t n_text_consts,
+                                                  const cstripe_value_set *sets, uint32_t n_sets,
+                                                  const cstripe_lookup *lookups, uint32_t n_lookups,
+                                                  const cstripe_expr *exprs, uint32_t n_exprs)
+{
     if (!r) { cs_set_err("scan_begin: null reader"); return nullptr; }
     auto *s = new cstripe_scan();
     s->r = r;
     s->cols_mask = cols_mask;
     if (n_preds > CSTRIPE_MAX_PREDS) { cs_set_err("too many predicates (max %d)", CSTRIPE_MAX_PREDS); delete s; return nullptr; }
     if (!lookups_begin(s, lookups, n_lookups)) { delete s; return nullptr; }
+    if (!exprs_begin(s, exprs, n_exprs)) { delete s; return nullptr; }
     {
         uint32_t n_inner = 0;
         for (const cs_lookup &lk : s->lookups) n_inner += lk.inner ? 1 : 0;
@@ -1464,13 +1560,14 @@ extern "C" cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t 
     for (uint32_t i = 0; i < n_preds; i++) {
         if (preds[i].column < r->head.column_count) continue;
         if (preds[i].column >= cs_scan_ncols(s)) {
-            cs_set_err("scan_begin: predicate %u: column %u out of range (%u table + %u derived columns)",
-                       i, preds[i].column, r->head.column_count, s->n_derived);
+            cs_set_err("scan_begin: predicate %u: column %u out of range (%u table + %u derived + %u computed columns)",
+                       i, preds[i].column, r->head.column_count, s->n_derived, (unsigned)s->exprs.size());
             delete s; return nullptr;
         }
         if (preds[i].op > CSTRIPE_PRED_NE) {
-            cs_set_err("scan_begin_lookups: predicate %u: op %u on derived column %u is not supported "
-                       "(LT..NE only; no IN / NOT IN)", i, preds[i].op, preds[i].column);
+            cs_set_err("scan_begin_lookups: predicate %u: op %u on %s column %u is not supported "
+                       "(LT..NE only; no IN / NOT IN)", i, preds[i].op,
+                       cs_col_expr(s, preds[i].column) ? "computed" : "derived", preds[i].column);
             delete s; return nullptr;
         }
     }
@@ -1613,7 +1710,7 @@ extern "C" cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t 
         for (const auto &p : s->preds)
             any_text |= cs_col_type(s, p.column) == CSTRIPE_TEXT ||
                         cs_col_type(s, p.column) == CSTRIPE_VARTEXT ||
-                        cs_col_derived(s, p.column);   /* nor about lookups */
+                        cs_col_derived(s, p.column);   /* nor about lookups and expressions */
         any_text |= any_set;     /* nor about value sets */
         std::vector<uint8_t> selmask;
         if (!s->preds.empty() && !any_text && dpv != 0 &&
@@ -1649,9 +1746,15 @@ extern "C" cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t 
                  * when `key_column IN keys` is */
                 const cs_lookup *g_lk = nullptr;
                 bool g_only_lk = true;
+                bool g_expr = false;   /* an atom on a computed column: the group never refutes */
                 while (j < s->preds.size() &&
                        s->preds[j].or_group == s->preds[i].or_group) {
                     const cstripe_pred &p = s->preds[j];
+                    if (cs_col_expr(s, p.column)) {
+                        g_expr = true;
+                        j++;
+                        continue;
+                    }
                     if (cs_col_derived(s, p.column)) {
                         const cs_lookup *lk = cs_col_lookup(s, p.column, nullptr);
                         if (g_lk && g_lk != lk) g_only_lk = false;
@@ -1699,6 +1802,7 @@ extern "C" cstripe_scan *cstripe_scan_begin_lookups(cstripe_reader *r, uint64_t 
                 if (g_lk)
                     group_refuted = g_only_lk &&
                                     lookup_refutes(*g_lk, st.nodes[g_lk->key_column][k].n);
+                if (g_expr) group_refuted = false;
                 if (group_refuted) selected = false;
                 i = j;
             }
@@ -1779,6 +1883,24 @@ extern "C" int cstripe_scan_last_lookup_ms(const cstripe_scan *s, double *build_
     if (!s) return CSTRIPE_ERR_ARG;
     if (build_ms) *build_ms = s->last_lookup_build_ms;
     if (probe_ms) *probe_ms = s->last_lookup_probe_ms;
+    return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_expr_range(const cstripe_scan *s, uint32_t e, int64_t *lo, int64_t *hi,
+                                       uint64_t *n_present)
+{
+    if (!s || e >= s->exprs.size()) { cs_set_err("scan_expr_range: expression %u is not an expression of this scan", e); return CSTRIPE_ERR_ARG; }
+    if (!s->gpu) { cs_set_err("scan_expr_range: scan not staged — the range is measured by cstripe_gpu_stage"); return CSTRIPE_ERR_NOGPU; }
+    if (lo) *lo = s->exprs[e].lo;
+    if (hi) *hi = s->exprs[e].hi;
+    if (n_present) *n_present = s->exprs[e].n_present;
+    return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_last_expr_ms(const cstripe_scan *s, double *eval_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (eval_ms) *eval_ms = s->last_expr_ms;
     return CSTRIPE_OK;
 }
 

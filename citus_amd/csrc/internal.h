@@ -98,12 +98,23 @@ struct cs_lookup {
     uint64_t form_size = 0;
 };
 
+/* one expression (cstripe_scan_begin_exprs): a postfix program evaluated at
+ * stage into a computed I64 column */
+struct cs_expr {
+    std::vector<cstripe_expr_op> ops;    /* validated copy of the program */
+    uint32_t first_col = 0;              /* its column id */
+    int64_t lo = 0, hi = 0;              /* measured at the last stage */
+    uint64_t n_present = 0;
+};
+
 struct cstripe_scan {
     cstripe_reader *r = nullptr;
     uint64_t cols_mask = 0;
     std::vector<cstripe_pred> preds;
     std::vector<cs_lookup> lookups;
     uint32_t n_derived = 0;                 /* payload columns of all lookups */
+    std::vector<cs_expr> exprs;             /* computed columns, after the derived */
+    double last_expr_ms = 0.0;              /* stage-time evaluation launches */
     double last_lookup_build_ms = 0.0;      /* stage-time lookup split */
     double last_lookup_probe_ms = 0.0;
     std::vector<cs_value_set> sets;         /* IN / NOT_IN preds: ival indexes these */
@@ -151,10 +162,11 @@ struct cstripe_scan {
 };
 
 /* Column addressing of a scan: ids below the table's column count are table
- * columns, the ids after them the derived (lookup payload) columns, I64. */
+ * columns, the ids after them the derived (lookup payload) columns, then the
+ * computed (expression) columns; both kinds are I64 and "derived" here. */
 static inline uint32_t cs_scan_ncols(const cstripe_scan *s)
 {
-    return s->r->head.column_count + s->n_derived;
+    return s->r->head.column_count + s->n_derived + (uint32_t)s->exprs.size();
 }
 static inline bool cs_col_derived(const cstripe_scan *s, uint32_t c)
 {
@@ -174,6 +186,13 @@ static inline const cs_lookup *cs_col_lookup(const cstripe_scan *s, uint32_t c, 
             return &lk;
         }
     return nullptr;
+}
+
+/* expression that computes column c, or null */
+static inline const cs_expr *cs_col_expr(const cstripe_scan *s, uint32_t c)
+{
+    const uint32_t first = s->r->head.column_count + s->n_derived;
+    return c >= first && c < cs_scan_ncols(s) ? &s->exprs[c - first] : nullptr;
 }
 
 /* implemented in cstripe_gpu.hip */

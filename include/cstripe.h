@@ -585,6 +585,118 @@ int cstripe_scan_last_lookup_ms(const cstripe_scan *s, double *build_ms, double 
 #define CSTRIPE_LOOKUP_FORM_HASH   1
 #define CSTRIPE_LOOKUP_FORM_DIRECT 2
 int cstripe_scan_lookup_form(const cstripe_scan *s, uint32_t lookup_idx, uint64_t *size);
+
+/* ---- expressions: device-computed columns ----
+ * The row-level expressions the reference evaluates in ExecQual / ExecProject
+ * over the rows ColumnarScanNext returns (columnar_customscan.c:1854-1913):
+ * column-versus-column comparisons, CASE inside an aggregate, arithmetic,
+ * extract(year). An expression is a small POSTFIX program over int64 values;
+ * cstripe_gpu_stage evaluates it once per row of the selected chunk groups
+ * and the result is a COMPUTED COLUMN every query surface addresses by a
+ * column id past the table's and the lookups' own. */
+#define CSTRIPE_MAX_EXPRS      8
+#define CSTRIPE_MAX_EXPR_OPS   48
+#define CSTRIPE_MAX_EXPR_DEPTH 8
+typedef enum cstripe_exop {
+    CSTRIPE_EX_COL = 0,   /* push column `column` (NULL when the row's value is NULL) */
+    CSTRIPE_EX_CONST,     /* push ival */
+    CSTRIPE_EX_NULL,      /* push NULL */
+    CSTRIPE_EX_ADD, CSTRIPE_EX_SUB, CSTRIPE_EX_MUL, CSTRIPE_EX_DIV, CSTRIPE_EX_MOD, CSTRIPE_EX_NEG,
+    CSTRIPE_EX_LT, CSTRIPE_EX_LE, CSTRIPE_EX_GT, CSTRIPE_EX_GE, CSTRIPE_EX_EQ, CSTRIPE_EX_NE,   /* -> 0 / 1 */
+    CSTRIPE_EX_AND, CSTRIPE_EX_OR, CSTRIPE_EX_NOT,      /* SQL three-valued; truth = nonzero; -> 0 / 1 / NULL */
+    CSTRIPE_EX_IS_NULL,                                  /* -> 0 / 1, never NULL */
+    CSTRIPE_EX_COALESCE,                                 /* (a b) -> a if a is not NULL else b */
+    CSTRIPE_EX_SELECT,                                   /* (c a b) -> a if c is non-NULL and nonzero else b: CASE WHEN c THEN a ELSE b */
+    CSTRIPE_EX_YEAR,                                     /* days since 1970-01-01 (this ABI's date32) -> proleptic Gregorian year */
+} cstripe_exop;
+typedef struct cstripe_expr_op { uint32_t op; uint32_t column; int64_t ival; } cstripe_expr_op;
+typedef struct cstripe_expr    { const cstripe_expr_op *ops; uint32_t n_ops; uint32_t _pad; } cstripe_expr;
+
+/* scan_begin_exprs: scan_begin_lookups plus expressions. With n_exprs == 0 it
+ * is exactly cstripe_scan_begin_lookups (which calls it). Programs are copied.
+ *  - Computed columns: expression e is column cstripe_column_count(r) + (all
+ *    lookup payloads) + e, type I64. It is always projected (no cols_mask bit)
+ *    and takes one of the 16 projected slots of a scan; overflow is
+ *    CSTRIPE_ERR_ARG from cstripe_gpu_stage, naming the expression, and leaves
+ *    the scan unstaged. Table plus derived plus computed columns must stay
+ *    <= 64. cstripe_scan_column_count counts them; for such a scan the
+ *    per-column arrays of cstripe_rows have that many entries.
+ *  - Inputs: EX_COL names a table column of type I8/I16/I32/I64 or a
+ *    lookup-derived column; every input column (and a lookup's key) is
+ *    projected implicitly. F32/F64/TEXT/VARTEXT columns and other computed
+ *    columns are refused at begin (SELECT nesting covers what chaining would).
+ *  - Value semantics, per row, those of PG int8. Every stack entry carries a
+ *    value, a NULL bit and an ERROR bit.
+ *      Strict ops — ADD SUB MUL DIV MOD NEG, the six comparisons, YEAR: a NULL
+ *      operand gives NULL and raises nothing (PG does not call a strict
+ *      function on NULL). With all operands non-NULL: ADD / SUB / MUL / NEG
+ *      beyond int64 is the error "bigint out of range"; DIV truncates toward
+ *      zero, a zero divisor is "division by zero", INT64_MIN / -1 is "bigint
+ *      out of range"; MOD takes the dividend's sign, a zero divisor is
+ *      "division by zero", x % -1 is 0; YEAR of a value outside
+ *      [-2^31, 2^31) is "year out of range". A comparison gives 0 / 1.
+ *      AND / OR / NOT are Kleene over truth = nonzero: FALSE AND NULL = FALSE,
+ *      TRUE OR NULL = TRUE, NOT NULL = NULL; results are 0 / 1 / NULL.
+ *      IS_NULL gives 0 / 1. COALESCE (a b) is a unless a is NULL, then b.
+ *      SELECT (c a b) is a when c is non-NULL and nonzero, else b.
+ *    Errors are lazy, like PG's: a strict op's result is in error if an
+ *    operand is or the op itself fails (a NULL result carries no error of the
+ *    op itself, only its operands'); SELECT is in error if c is, otherwise it
+ *    takes only the chosen branch's bit; COALESCE takes a's bit, and b's only
+ *    when a is NULL; AND / OR evaluate left to right, and a clean left operand
+ *    that decides the result (FALSE for AND, TRUE for OR) hides the right
+ *    operand's error; NOT and IS_NULL pass their operand's bit on. So
+ *    `CASE WHEN b <> 0 THEN a / b ELSE 0 END` is safe.
+ *  - If the FINAL value of any row of any selected chunk group is in error,
+ *    cstripe_gpu_stage returns CSTRIPE_ERR_ARG with "expression <e>: division
+ *    by zero" / "bigint out of range" / "year out of range" and the scan is
+ *    left unstaged.
+ *  - The one deviation from PG: the stage evaluates EVERY row of the selected
+ *    chunk groups, including rows the scan's predicates would reject (PG would
+ *    have filtered them before ExecProject). Guard such cases with SELECT.
+ *  - A computed id is accepted as the predicate column of LT..NE (a NULL
+ *    operand fails the atom; column-versus-column is `computed == 1`), as the
+ *    operand of COUNT_COL and every I64 aggregate kind in any operand
+ *    position, as a cstripe_scan_agg_hashed / _hashed_topn key and KEY order
+ *    term, as a cstripe_scan_select_topn order column, and as a wanted column
+ *    of cstripe_scan_select / _select_topn. Refused with a message: IN /
+ *    NOT_IN on it, cstripe_scan_agg_grouped keys, a lookup key column.
+ *    cstripe_scan_next_batch and cstripe_read_row do not know it.
+ *  - Key packing: the column's [lo, hi] and non-NULL count are measured by the
+ *    evaluation kernel at stage (cstripe_scan_expr_range).
+ *  - Errors at begin (NULL, message naming the expression and op index):
+ *    n_exprs > CSTRIPE_MAX_EXPRS, n_ops 0 or above CSTRIPE_MAX_EXPR_OPS, an
+ *    unknown op, stack underflow, depth above CSTRIPE_MAX_EXPR_DEPTH, a final
+ *    depth other than 1, a bad or wrongly typed column.
+ *  - Chunk refutation: an atom on a computed column never refutes, and the
+ *    device prune kernel is skipped when one is present. A caller who wants
+ *    pruning adds a redundant predicate on the base column.
+ *  - Device evaluation: all at cstripe_gpu_stage, after the lookups; no query
+ *    kernel knows about expressions. One launch per expression, one block per
+ *    chunk group, writes the column's exists bitmap, rank table and compacted
+ *    values; it then reads as an ordinary sparse I64 column in scratch. Such
+ *    scans report CSTRIPE_AGG_PATH_GENERAL. A restage re-evaluates.
+ *  - Out of scope: float / TEXT / VARTEXT operands or results, expressions
+ *    over other expressions or over aggregates, LIKE, pruning through an
+ *    expression, a dense result form, computed columns in next_batch /
+ *    read_row. */
+cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t cols_mask,
+                                       const cstripe_pred *preds, uint32_t n_preds,
+                                       const cstripe_text_const *text_consts,
+                                       uint32_t n_text_consts,
+                                       const cstripe_value_set *sets, uint32_t n_sets,
+                                       const cstripe_lookup *lookups, uint32_t n_lookups,
+                                       const cstripe_expr *exprs, uint32_t n_exprs);
+/* [min, max] and non-NULL count of computed column e over the selected chunk
+ * groups, measured at the last stage; an all-NULL column reports
+ * n_present = 0, lo = hi = 0. CSTRIPE_ERR_NOGPU on an unstaged scan,
+ * CSTRIPE_ERR_ARG when e is not an expression of this scan. Any out pointer
+ * may be NULL. */
+int cstripe_scan_expr_range(const cstripe_scan *s, uint32_t e, int64_t *lo, int64_t *hi,
+                            uint64_t *n_present);
+/* device time (hipEvents, milliseconds) of the last cstripe_gpu_stage's
+ * evaluation launches, all expressions together; 0 without an expression */
+int cstripe_scan_last_expr_ms(const cstripe_scan *s, double *eval_ms);
 void cstripe_scan_end(cstripe_scan *s);
 int64_t cstripe_scan_chunk_groups_filtered(const cstripe_scan *s);
 
