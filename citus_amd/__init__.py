@@ -46,6 +46,9 @@ VARTEXT_MAX_DISTINCT = 1 << 20
 COMP_NONE, COMP_PGLZ, COMP_LZ4, COMP_ZSTD = 0, 1, 2, 3
 PRED_LT, PRED_LE, PRED_GT, PRED_GE, PRED_EQ, PRED_NE = range(6)
 PRED_IN, PRED_NOT_IN = 6, 7      # value is a set (see make_preds_sets)
+PRED_LIKE, PRED_NOT_LIKE = 8, 9  # value is the pattern (bytes / str), VARTEXT only
+LIKE_MAX_PATTERN = 256
+LIKE_FORM_NONE, LIKE_FORM_DICT, LIKE_FORM_STREAM = 0, 1, 2
 MAX_SETS = 4
 MAX_SET_VALUES = 1 << 26
 SET_FORM_NONE, SET_FORM_HASH, SET_FORM_BITMAP = 0, 1, 2
@@ -450,6 +453,11 @@ _last_set_ms = _sig("cstripe_scan_last_set_ms", C.c_int,
                     [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)])
 _set_form = _sig("cstripe_scan_set_form", C.c_int,
                  [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)])
+_like_match = _sig("cstripe_like_match", C.c_int,
+                   [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32])
+_last_like_ms = _sig("cstripe_scan_last_like_ms", C.c_int,
+                     [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)])
+_like_form = _sig("cstripe_scan_like_form", C.c_int, [C.c_void_p, C.c_uint32])
 _vartext_validate = _sig("cstripe_vartext_validate", C.c_int,
                          [C.c_char_p, C.c_uint64, C.c_uint32])
 _text_dict = _sig("cstripe_scan_text_dict", C.c_int,
@@ -617,6 +625,19 @@ def vartext_pack(values):
     if any(v is None for v in values):
         nulls = np.array([1 if v is None else 0 for v in values], dtype=np.uint8)
     return offs, data, nulls
+
+
+def like_match(pattern, value):
+    """cstripe_like_match: whether `value` matches the LIKE `pattern` (bytes
+    or str each) — PG LIKE, default escape, "C" collation, UTF-8 characters;
+    the matcher source the device runs. Raises CStripeError for a pattern
+    scan_begin would refuse."""
+    p = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    v = value.encode() if isinstance(value, str) else bytes(value)
+    rc = _like_match(p, len(p), v, len(v))
+    if rc < 0:
+        raise CStripeError(f"like_match failed (rc={rc}): {errmsg()}")
+    return bool(rc)
 
 
 def vartext_validate(stream, n_values):
@@ -1262,8 +1283,9 @@ class Scan:
         # pred columns are implicitly projected (scan_begin does the same)
         ntab = reader.column_count
         self._mask = cols_mask & ((1 << ntab) - 1)
+        # (a column that is only pattern-matched has no values to read)
         for p in preds:
-            if p[0] < ntab:
+            if p[0] < ntab and p[1] not in (PRED_LIKE, PRED_NOT_LIKE):
                 self._mask |= 1 << p[0]
         for lk in lookups:
             self._mask |= 1 << lk.key_col        # key columns are read too
@@ -1347,6 +1369,19 @@ class Scan:
         _check(_last_text_ms(self._h, C.byref(d), C.byref(w), C.byref(t), C.byref(m)),
                "scan_last_text_ms")
         return d.value, w.value, t.value, m.value
+
+    def last_like_ms(self):
+        """(match, apply) device ms of the last stage()'s LIKE / NOT LIKE
+        work, all patterns together; zeros without one"""
+        m, a = C.c_double(), C.c_double()
+        _check(_last_like_ms(self._h, C.byref(m), C.byref(a)), "scan_last_like_ms")
+        return m.value, a.value
+
+    def like_form(self, col):
+        """read form of a pattern-matched VARTEXT column at the last stage():
+        None (unstaged, or no LIKE atom on it), "dict" or "stream" """
+        return {LIKE_FORM_DICT: "dict", LIKE_FORM_STREAM: "stream"}.get(
+            _like_form(self._h, col))
 
     def last_set_ms(self):
         """(build, probe) device ms of the last stage()'s set work (IN /

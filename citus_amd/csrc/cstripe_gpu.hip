@@ -27,6 +27,7 @@
 #include "zstd_r.h"
 #include "lz4_enc.h"
 #include "vartext.h"
+#include "like.h"
 
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -221,9 +222,14 @@ struct cs_gpu_state {
     /* IN / NOT IN: one member slot (a projected I8 membership column in
      * scratch, after the table columns) per distinct (column, set) pair;
      * mpred_slot is parallel to scan->preds, -1 for every other predicate */
-    struct MemberSlot { uint32_t col, set, proj; };
+    struct MemberSlot { uint32_t col, set, proj; bool like; };
     std::vector<MemberSlot> mslots;
     std::vector<int> mpred_slot;
+    /* LIKE / NOT LIKE: a member slot too, one per distinct (column, pattern
+     * bytes) pair — `like` set, `set` the index of a text constant holding
+     * the pattern; filled by vartext_build, skipped by sets_build.
+     * like_form[table column] is the CSTRIPE_LIKE_FORM_* of this stage. */
+    std::vector<uint8_t> like_form;
     std::vector<void *> set_bufs;    /* set and lookup tables (sets_build,
                                       * lookups_build) */
     /* lookups: one derived slot (a projected sparse I64 column in scratch,
@@ -3476,25 +3482,47 @@ int csgpu_stage(cstripe_scan *s, int device_id)
     g->mpred_slot.assign(s->preds.size(), -1);
     for (size_t i = 0; i < s->preds.size(); i++) {
         const cstripe_pred &q = s->preds[i];
-        if (q.op != CSTRIPE_PRED_IN && q.op != CSTRIPE_PRED_NOT_IN) continue;
+        const bool like = cs_pred_is_like(q);
+        if (q.op != CSTRIPE_PRED_IN && q.op != CSTRIPE_PRED_NOT_IN && !like) continue;
         int found = -1;
-        for (size_t m = 0; m < g->mslots.size(); m++)
-            if (g->mslots[m].col == q.column && g->mslots[m].set == (uint32_t)q.ival) found = (int)m;
+        for (size_t m = 0; m < g->mslots.size(); m++) {
+            const auto &ms = g->mslots[m];
+            if (ms.col != q.column || ms.like != like) continue;
+            if (like ? s->text_consts[ms.set] == s->text_consts[(size_t)q.ival]
+                     : ms.set == (uint32_t)q.ival) found = (int)m;
+        }
         if (found < 0) {
             if (n_proj >= MAX_PROJ) {
                 cs_set_err("gpu_stage: %u projected columns plus the membership columns of the "
-                           "IN / NOT IN predicates exceed the %d slots of one scan", n_tab, MAX_PROJ);
+                           "IN / NOT IN and LIKE / NOT LIKE predicates exceed the %d slots of one "
+                           "scan", n_tab, MAX_PROJ);
                 csgpu_release(s);
                 return CSTRIPE_ERR_ARG;
             }
             found = (int)g->mslots.size();
-            g->mslots.push_back({q.column, (uint32_t)q.ival, n_proj});
+            g->mslots.push_back({q.column, (uint32_t)q.ival, n_proj, like});
             g->proj_type[n_proj] = CSTRIPE_I8;
             n_proj++;
         }
         g->mpred_slot[i] = found;
     }
     if (!g->mslots.empty()) g->fusable = false;
+    /* read form of the pattern-matched columns: STREAM when nothing reads the
+     * column's values (need_mask), DICT otherwise; CSTRIPE_LIKE_FORM=dict
+     * forces DICT, =stream changes nothing (a column that needs ranks keeps
+     * them) */
+    g->like_form.assign(r->head.column_count, CSTRIPE_LIKE_FORM_NONE);
+    {
+        const char *lf = getenv("CSTRIPE_LIKE_FORM");
+        const bool force_dict = lf && !strcmp(lf, "dict");
+        for (const auto &ms : g->mslots)
+            if (ms.like)
+                g->like_form[ms.col] = (uint8_t)(
+                    (s->need_mask & (1ull << ms.col)) || force_dict ? CSTRIPE_LIKE_FORM_DICT
+                                                                    : CSTRIPE_LIKE_FORM_STREAM);
+    }
+    s->like_forms = g->like_form;
+    s->last_like_match_ms = s->last_like_apply_ms = 0;
     /* derived slots of the lookups' payload columns, after the member slots */
     for (size_t l = 0; l < s->lookups.size(); l++)
         for (uint32_t pl = 0; pl < s->lookups[l].n_payloads; pl++) {
@@ -3546,8 +3574,10 @@ int csgpu_stage(cstripe_scan *s, int device_id)
             if (r->cols[c].type == CSTRIPE_VARTEXT) {
                 /* read as int32 dictionary ranks: n_present entries in a
                  * scratch region no decode segment writes (vartext_build);
-                 * the byte stream itself is staged to temporary buffers */
-                scratch_bytes = align_up(scratch_bytes, 16) + align_up((uint64_t)nd.n.n_present * 4, 16);
+                 * the byte stream itself is staged to temporary buffers. A
+                 * STREAM-form column is only pattern-matched: no ranks */
+                if (g->like_form[c] != CSTRIPE_LIKE_FORM_STREAM)
+                    scratch_bytes = align_up(scratch_bytes, 16) + align_up((uint64_t)nd.n.n_present * 4, 16);
                 any_vartext = true;
                 if (nd.n.n_present != nd.n.row_count)
                     rank_words += (rows + 63) / 64;
@@ -3713,9 +3743,12 @@ int csgpu_stage(cstripe_scan *s, int device_id)
                 cl.type = CSTRIPE_I32;
                 cl.width = 4;
                 cl.flags |= 1;
-                spos = align_up(spos, 16);
-                cl.val_off = spos;
-                spos += align_up((uint64_t)nd.n.n_present * 4, 16);
+                if (g->like_form[c] != CSTRIPE_LIKE_FORM_STREAM) {
+                    spos = align_up(spos, 16);
+                    cl.val_off = spos;
+                    spos += align_up((uint64_t)nd.n.n_present * 4, 16);
+                }   /* else: no rank region; every surface that would read
+                     * the column refuses it (like_stream_refused) */
                 g->fusable = false;
                 h_colloc[(uint64_t)gi * n_proj + pj] = cl;
                 continue;
@@ -4019,7 +4052,9 @@ int csgpu_stage(cstripe_scan *s, int device_id)
         }
     }
     s->last_set_build_ms = s->last_set_probe_ms = 0;
-    if (!g->mslots.empty()) {
+    bool any_set_slot = false;
+    for (const auto &ms : g->mslots) any_set_slot |= !ms.like;
+    if (any_set_slot) {
         VtTemps st;
         int rc = sets_build(s, st);
         st.release();
@@ -4341,6 +4376,75 @@ __global__ __launch_bounds__(AGG_BLOCK) void vt_remap_kernel(
         dst[i] = (int32_t)slot2rank[vs[i]];
 }
 
+/* ---- LIKE / NOT LIKE (cstripe.h): the pattern travels by value in the
+ * kernel argument; one lane matches one value with cslk_match (like.h), whose
+ * reads stay inside [ref >> 16, +len) of the temp buffer — bounds the walk
+ * checked. Lanes of a wave diverge on value length; long values are not
+ * split across lanes. ---- */
+struct LikePat {
+    uint32_t len;
+    uint8_t b[CSLK_MAX_PATTERN];
+};
+
+#define VT_LIKE_VALS 4u                         /* values per lane */
+#define VT_LIKE_TILE (AGG_BLOCK * VT_LIKE_VALS)
+
+/* DICT form: one lane per dictionary entry, a 0/1 byte per table slot */
+__global__ __launch_bounds__(AGG_BLOCK) void vt_like_kernel(
+    const uint8_t *__restrict__ raw, const VtEntry *__restrict__ entries,
+    uint32_t n_dict, uint8_t *__restrict__ flag, const LikePat pat)
+{
+    for (uint32_t e = blockIdx.x * AGG_BLOCK + threadIdx.x; e < n_dict;
+         e += gridDim.x * AGG_BLOCK) {
+        const VtEntry en = entries[e];
+        flag[en.slot] = (uint8_t)cslk_match(pat.b, pat.len, raw + (en.ref >> 16),
+                                            (uint32_t)(en.ref & 0xFFFFu));
+    }
+}
+
+/* DICT form: one block per chunk-column, member[i] = flag[vslot[i]]; lane:
+ * four consecutive values, one dword of 0/1 bytes. The member region is
+ * padded to 16 bytes, so the tail dword stays inside it. */
+__global__ __launch_bounds__(AGG_BLOCK) void vt_like_apply_kernel(
+    const VtChunk *__restrict__ chunks, const uint64_t *__restrict__ member_off,
+    const uint32_t *__restrict__ vslot, uint64_t vbeg, const uint8_t *__restrict__ flag,
+    uint8_t *__restrict__ scratch)
+{
+    const VtChunk ck = chunks[blockIdx.x];
+    uint8_t *dst = scratch + member_off[blockIdx.x];
+    const uint32_t *vs = vslot + (ck.val_base - vbeg);
+    for (uint32_t v0 = threadIdx.x * VT_LIKE_VALS; v0 < ck.n_present; v0 += VT_LIKE_TILE) {
+        uint32_t word = 0;
+        #pragma unroll
+        for (uint32_t k = 0; k < VT_LIKE_VALS; k++)
+            if (v0 + k < ck.n_present) word |= (uint32_t)flag[vs[v0 + k]] << (8u * k);
+        *(uint32_t *)(dst + v0) = word;
+    }
+}
+
+/* STREAM form: one block per (chunk-column, tile of VT_LIKE_TILE values),
+ * matching straight off the walk's (offset, length) words; the same lane
+ * shape and store as above */
+__global__ __launch_bounds__(AGG_BLOCK) void vt_like_stream_kernel(
+    const uint8_t *__restrict__ raw, const unsigned long long *__restrict__ vpos,
+    const VtChunk *__restrict__ chunks, const uint64_t *__restrict__ member_off,
+    uint32_t tiles_pc, uint8_t *__restrict__ scratch, const LikePat pat)
+{
+    const uint32_t ci = blockIdx.x / tiles_pc, tile = blockIdx.x % tiles_pc;
+    const VtChunk ck = chunks[ci];
+    const uint32_t v0 = (tile * AGG_BLOCK + threadIdx.x) * VT_LIKE_VALS;
+    if (v0 >= ck.n_present) return;
+    uint32_t word = 0;
+    #pragma unroll
+    for (uint32_t k = 0; k < VT_LIKE_VALS; k++) {
+        if (v0 + k >= ck.n_present) break;
+        const unsigned long long ref = vpos[ck.val_base + v0 + k];
+        word |= (uint32_t)cslk_match(pat.b, pat.len, raw + (ref >> 16),
+                                     (uint32_t)(ref & 0xFFFFu)) << (8u * k);
+    }
+    *(uint32_t *)(scratch + member_off[ci] + v0) = word;
+}
+
 /* memcmp order, the shorter string first on a prefix tie */
 static inline int vt_cmp(const uint8_t *a, size_t al, const uint8_t *b, size_t bl)
 {
@@ -4427,7 +4531,8 @@ static int vartext_build(cstripe_scan *s, VtTemps &vt)
     col_cbeg[vcols.size()] = chunks.size();
     col_vbeg[vcols.size()] = n_values;
     for (size_t ci = 0; ci < vcols.size(); ci++) {
-        s->text_dicts[vcols[ci]].built = true;
+        /* a STREAM-form column gets no dictionary (cstripe_scan_text_dict) */
+        s->text_dicts[vcols[ci]].built = g->like_form[vcols[ci]] != CSTRIPE_LIKE_FORM_STREAM;
         s->text_dicts[vcols[ci]].offsets.assign(1, 0);
     }
 
@@ -4555,12 +4660,81 @@ static int vartext_build(cstripe_scan *s, VtTemps &vt)
             return CSTRIPE_ERR_FORMAT;
         }
 
+        /* the LIKE member slots of column vcols[ci], one pattern at a time:
+         * STREAM (d_ent null) matches every value off d_vpos; DICT matches
+         * the n_dict entries into a flag byte per table slot, then applies
+         * the flags through d_vslot */
+        auto like_build = [&](size_t ci, const VtEntry *d_ent, uint32_t n_dict, uint64_t slots,
+                              const uint32_t *d_vslot) -> int {
+            const uint32_t c = vcols[ci];
+            const uint32_t ncks = (uint32_t)(col_cbeg[ci + 1] - col_cbeg[ci]);
+            uint32_t max_np = 0;
+            for (uint64_t k = col_cbeg[ci]; k < col_cbeg[ci + 1]; k++)
+                max_np = std::max(max_np, chunks[k].n_present);
+            const uint32_t tiles_pc = std::max(1u, (max_np + VT_LIKE_TILE - 1) / VT_LIKE_TILE);
+            if ((uint64_t)ncks * tiles_pc >= (1ull << 31)) { cs_set_err("gpu_stage: too many tiles for the LIKE match"); return CSTRIPE_ERR_ARG; }
+            for (const auto &ms : g->mslots) {
+                if (!ms.like || ms.col != c) continue;
+                const uint32_t mark = vt.n_bufs;
+                const std::string &ptx = s->text_consts[ms.set];
+                LikePat pat{};
+                if (ptx.size() > CSLK_MAX_PATTERN) { cs_set_err("gpu_stage: LIKE pattern too long"); return CSTRIPE_ERR; }
+                pat.len = (uint32_t)ptx.size();
+                memcpy(pat.b, ptx.data(), ptx.size());
+                std::vector<uint64_t> moff(ncks);
+                for (uint32_t gi = 0; gi < ncks; gi++)
+                    moff[gi] = g->colloc_host[(uint64_t)gi * n_proj + ms.proj].val_off;
+                uint64_t *d_moff = nullptr;
+                uint8_t *d_flag = nullptr;
+                HIP_TRY(vt.alloc(d_moff, ncks * sizeof(uint64_t)));
+                HIP_TRY(hipMemcpyAsync(d_moff, moff.data(), ncks * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
+                if (d_ent) {
+                    HIP_TRY(vt.alloc(d_flag, slots));
+                    HIP_TRY(hipMemsetAsync(d_flag, 0, slots, g->stream));
+                }
+                HIP_TRY(hipEventRecord(vt.ev[3], g->stream));
+                if (d_ent) {
+                    if (n_dict)
+                        hipLaunchKernelGGL(vt_like_kernel, dim3((n_dict + AGG_BLOCK - 1) / AGG_BLOCK),
+                                           dim3(AGG_BLOCK), 0, g->stream, t_raw, d_ent, n_dict, d_flag, pat);
+                } else {
+                    hipLaunchKernelGGL(vt_like_stream_kernel, dim3(ncks * tiles_pc), dim3(AGG_BLOCK), 0,
+                                       g->stream, t_raw, d_vpos, d_chunks + col_cbeg[ci], d_moff,
+                                       tiles_pc, g->d_scratch, pat);
+                }
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(vt.ev[4], g->stream));
+                if (d_ent) {
+                    hipLaunchKernelGGL(vt_like_apply_kernel, dim3(ncks), dim3(AGG_BLOCK), 0, g->stream,
+                                       d_chunks + col_cbeg[ci], d_moff, d_vslot, col_vbeg[ci], d_flag,
+                                       g->d_scratch);
+                    HIP_TRY(hipGetLastError());
+                }
+                HIP_TRY(hipEventRecord(vt.ev[7], g->stream));
+                HIP_TRY(hipStreamSynchronize(g->stream));
+                float lms = 0;
+                (void)hipEventElapsedTime(&lms, vt.ev[3], vt.ev[4]);
+                s->last_like_match_ms += lms;
+                if (d_ent) {
+                    (void)hipEventElapsedTime(&lms, vt.ev[4], vt.ev[7]);
+                    s->last_like_apply_ms += lms;
+                }
+                vt.free_from(mark);
+            }
+            return CSTRIPE_OK;
+        };
+
         /* ---- per column: dictionary, gather, host sort, remap ---- */
         for (size_t ci = 0; ci < vcols.size(); ci++) {
             const uint32_t c = vcols[ci];
             const uint64_t vbeg = col_vbeg[ci], nv = col_vbeg[ci + 1] - vbeg;
             const uint32_t ncks = (uint32_t)(col_cbeg[ci + 1] - col_cbeg[ci]);
             if (nv == 0) continue;             /* all NULL: empty dictionary */
+            if (g->like_form[c] == CSTRIPE_LIKE_FORM_STREAM) {
+                /* only pattern-matched: no table, no gather, no sort, no ranks */
+                { int _rc = like_build(ci, nullptr, 0, 0, nullptr); if (_rc != CSTRIPE_OK) return _rc; }
+                continue;
+            }
             const uint32_t mark = vt.n_bufs;
             const uint64_t cap = std::min<uint64_t>(max_distinct, nv);
             uint64_t slots = 2;
@@ -4646,6 +4820,10 @@ static int vartext_build(cstripe_scan *s, VtTemps &vt)
             HIP_TRY(hipStreamSynchronize(g->stream));
             (void)hipEventElapsedTime(&ms, vt.ev[5], vt.ev[6]);
             s->last_text_remap_ms += ms;
+            if (g->like_form[c] == CSTRIPE_LIKE_FORM_DICT) {
+                int _rc = like_build(ci, d_ent, n_dict, slots, d_vslot);
+                if (_rc != CSTRIPE_OK) return _rc;
+            }
             vt.free_from(mark);
         }
     }
@@ -4882,7 +5060,7 @@ static int sets_build(cstripe_scan *s, VtTemps &st)
      * regions rely on too. */
     bool need_decode = false;
     for (const auto &ms : g->mslots)
-        if (g->col_scratch[(size_t)g->proj_of_col[ms.col]]) need_decode = true;
+        if (!ms.like && g->col_scratch[(size_t)g->proj_of_col[ms.col]]) need_decode = true;
     if (need_decode) {
         HIP_TRY(hipMemsetAsync(g->d_error, 0, sizeof(int), g->stream));
         { int _rc = launch_decode(g); if (_rc != CSTRIPE_OK) return _rc; }
@@ -4904,6 +5082,7 @@ static int sets_build(cstripe_scan *s, VtTemps &st)
     float ms_f = 0;
 
     for (const auto &ms : g->mslots) {
+        if (ms.like) continue;             /* filled by vartext_build */
         cs_value_set &vs = s->sets[ms.set];
         const bool vartext = r->cols[ms.col].type == CSTRIPE_VARTEXT;
         Built local;
@@ -5784,11 +5963,12 @@ static void fill_preds(const cstripe_scan *s, AggParams &p)
             p.preds[i].fval = 0.0;
         }
         if (g->mpred_slot[i] >= 0) {
-            /* IN / NOT IN: one integer atom over the membership column */
+            /* IN / NOT IN, LIKE / NOT LIKE: one integer atom over the
+             * membership column */
             p.preds[i].proj = (uint16_t)g->mslots[(size_t)g->mpred_slot[i]].proj;
             p.preds[i].op = CSTRIPE_PRED_EQ;
             p.preds[i].is_float = 0;
-            p.preds[i].ival = q.op == CSTRIPE_PRED_IN ? 1 : 0;
+            p.preds[i].ival = (q.op == CSTRIPE_PRED_IN || q.op == CSTRIPE_PRED_LIKE) ? 1 : 0;
             p.preds[i].fval = 0.0;
         }
     }
@@ -5797,6 +5977,19 @@ static void fill_preds(const cstripe_scan *s, AggParams &p)
 /* projected slot of a table or derived column id — with cs_col_type the one
  * place that answers "type / slot of column id c" — -1 when out of range or
  * not projected */
+/* true, with the error set, when `col` is a VARTEXT column staged in the
+ * LIKE stream form: it was only pattern-matched and has no ranks to read */
+static bool like_stream_refused(const cstripe_scan *s, int64_t col, const char *what)
+{
+    const cs_gpu_state *g = s->gpu;
+    if (col < 0 || col >= (int64_t)g->like_form.size() ||
+        g->like_form[(size_t)col] != CSTRIPE_LIKE_FORM_STREAM)
+        return false;
+    cs_set_err("%s: column %lld is only pattern-matched (LIKE stream form) and has no values to "
+               "read — add it to cols_mask", what, (long long)col);
+    return true;
+}
+
 static int proj_of(const cstripe_scan *s, int32_t col)
 {
     if (col < 0 || col >= (int32_t)cs_scan_ncols(s)) return -1;
@@ -5820,6 +6013,7 @@ static int fill_agg_params(const cstripe_scan *s, const cstripe_agg_spec *aggs,
         p.aggs[i].kind = (uint8_t)aggs[i].kind;
         p.aggs[i].one = aggs[i].one;
         int pa = proj_of(s, aggs[i].col_a), pb = proj_of(s, aggs[i].col_b), pc = proj_of(s, aggs[i].col_c);
+        if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && like_stream_refused(s, aggs[i].col_a, "agg operand")) return CSTRIPE_ERR_ARG;
         if (aggs[i].kind != CSTRIPE_AGG_COUNT_STAR && pa < 0) { cs_set_err("agg %u: col_a not projected", i); return CSTRIPE_ERR_ARG; }
         if (agg_reads_vartext(r, aggs[i])) { cs_set_err("agg %u: a VARTEXT column can only be the operand of COUNT_COL", i); return CSTRIPE_ERR_ARG; }
         p.aggs[i].proj_a = (uint8_t)(pa < 0 ? 0 : pa);
@@ -6807,6 +7001,7 @@ int csgpu_select(cstripe_scan *s, cstripe_rows *out, uint64_t capacity,
     for (uint32_t c = 0; c < n_cols && out->col_values; c++) {
         if (!out->col_values[c]) continue;
         const int pj = proj_of(s, (int32_t)c);
+        if (like_stream_refused(s, c, "scan_select")) return CSTRIPE_ERR_ARG;
         if (pj < 0) { cs_set_err("scan_select: column %u not projected", c); return CSTRIPE_ERR_ARG; }
         widths[sp.n_cols] = (uint8_t)csf_type_width(cs_col_type(s, c));
         dst_col[sp.n_cols] = c;
@@ -7300,6 +7495,7 @@ static int hash_prepare(cstripe_scan *s, const cstripe_agg_spec *aggs, uint32_t 
     for (uint32_t k = 0; k < n_key_cols; k++) {
         const uint32_t col = key_cols[k];
         const int pj = proj_of(s, (int32_t)col);
+        if (like_stream_refused(s, col, "scan_agg_hashed key")) return CSTRIPE_ERR_ARG;
         if (pj < 0) { cs_set_err("scan_agg_hashed: key col %u not projected", col); return CSTRIPE_ERR_ARG; }
         if (!out->keys[k] || !out->key_nulls[k]) { cs_set_err("scan_agg_hashed: no destination for key col %u", k); return CSTRIPE_ERR_ARG; }
         const uint8_t t = cs_col_type(s, col);
@@ -7922,6 +8118,7 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
     uint8_t otype[CSTRIPE_MAX_ORDER_COLS] = {0};
     for (uint32_t k = 0; k < n_order; k++) {
         const uint32_t col = order[k].column;
+        if (like_stream_refused(s, col, "scan_select_topn order")) return CSTRIPE_ERR_ARG;
         if (proj_of(s, (int32_t)col) < 0) {
             cs_set_err("scan_select_topn: order col %u not projected", col);
             return CSTRIPE_ERR_ARG;
@@ -7958,6 +8155,7 @@ int csgpu_select_topn(cstripe_scan *s, const cstripe_order_key *order, uint32_t 
     for (uint32_t c = 0; c < n_cols && out->col_values; c++) {
         if (!out->col_values[c]) continue;
         const int pj = proj_of(s, (int32_t)c);
+        if (like_stream_refused(s, c, "scan_select_topn")) return CSTRIPE_ERR_ARG;
         if (pj < 0) { cs_set_err("scan_select_topn: column %u not projected", c); return CSTRIPE_ERR_ARG; }
         widths[sp.n_cols] = (uint8_t)csf_type_width(cs_col_type(s, c));
         dst_col[sp.n_cols] = c;

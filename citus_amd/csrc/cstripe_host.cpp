@@ -23,6 +23,7 @@
 #include "pglz.h"
 #include "zstd_r.h"
 #include "vartext.h"
+#include "like.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1547,6 +1548,7 @@ extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t co
     if (n_preds > CSTRIPE_MAX_PREDS) { cs_set_err("too many predicates (max %d)", CSTRIPE_MAX_PREDS); delete s; return nullptr; }
     if (!lookups_begin(s, lookups, n_lookups)) { delete s; return nullptr; }
     if (!exprs_begin(s, exprs, n_exprs)) { delete s; return nullptr; }
+    s->need_mask = s->cols_mask;   /* the caller's columns and the expressions' inputs */
     {
         uint32_t n_inner = 0;
         for (const cs_lookup &lk : s->lookups) n_inner += lk.inner ? 1 : 0;
@@ -1566,7 +1568,7 @@ extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t co
         }
         if (preds[i].op > CSTRIPE_PRED_NE) {
             cs_set_err("scan_begin_lookups: predicate %u: op %u on %s column %u is not supported "
-                       "(LT..NE only; no IN / NOT IN)", i, preds[i].op,
+                       "(LT..NE only; no IN / NOT IN, no LIKE / NOT LIKE)", i, preds[i].op,
                        cs_col_expr(s, preds[i].column) ? "computed" : "derived", preds[i].column);
             delete s; return nullptr;
         }
@@ -1620,8 +1622,36 @@ extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t co
                 s->preds.back().or_group = 0xFFFFFF00u + i;
             continue;
         }
-        if (preds[i].op > CSTRIPE_PRED_NOT_IN) { cs_set_err("scan_begin: predicate %u has unknown op %u", i, preds[i].op); delete s; return nullptr; }
-        if (pred_is_set(preds[i])) {
+        if (preds[i].op > CSTRIPE_PRED_NOT_LIKE) { cs_set_err("scan_begin: predicate %u has unknown op %u", i, preds[i].op); delete s; return nullptr; }
+        if (cs_pred_is_like(preds[i])) {
+            const char *name = preds[i].op == CSTRIPE_PRED_LIKE ? "LIKE" : "NOT LIKE";
+            if (r->cols[preds[i].column].type != CSTRIPE_VARTEXT) {
+                cs_set_err("scan_begin: predicate %u: op %u (%s) needs a VARTEXT column, column %u "
+                           "is not one", i, preds[i].op, name, preds[i].column);
+                delete s; return nullptr;
+            }
+            if (preds[i].ival < 0 || (uint64_t)preds[i].ival >= n_text_consts) {
+                cs_set_err("scan_begin: predicate %u is %s: ival %lld is not an index into the "
+                           "%u text constants (cstripe_scan_begin_ex)", i, name,
+                           (long long)preds[i].ival, n_text_consts);
+                delete s; return nullptr;
+            }
+            const std::string &pat = s->text_consts[(size_t)preds[i].ival];
+            const int bad = pat.size() > CSTRIPE_LIKE_MAX_PATTERN ? 1 :
+                            cslk_check_pattern((const uint8_t *)pat.data(), (uint32_t)pat.size());
+            if (bad) {
+                if (bad == 1)
+                    cs_set_err("scan_begin: predicate %u: %s pattern of %llu bytes is longer than "
+                               "CSTRIPE_LIKE_MAX_PATTERN (%d)", i, name,
+                               (unsigned long long)pat.size(), CSTRIPE_LIKE_MAX_PATTERN);
+                else if (bad == 2)
+                    cs_set_err("scan_begin: predicate %u: LIKE pattern must not end with escape "
+                               "character", i);
+                else
+                    cs_set_err("scan_begin: predicate %u: %s pattern is not valid UTF-8", i, name);
+                delete s; return nullptr;
+            }
+        } else if (pred_is_set(preds[i])) {
             const uint8_t t = r->cols[preds[i].column].type;
             if (preds[i].ival < 0 || (uint64_t)preds[i].ival >= n_sets) {
                 cs_set_err("scan_begin: predicate %u is IN / NOT IN: ival %lld is not an index "
@@ -1656,12 +1686,14 @@ extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t co
         if (s->preds.back().or_group == 0)
             s->preds.back().or_group = 0xFFFFFF00u + i;   /* private ids */
         s->cols_mask |= 1ull << preds[i].column;   /* pred columns must be read */
+        if (!cs_pred_is_like(preds[i])) s->need_mask |= 1ull << preds[i].column;
     }
     /* lookups: key columns are read; INNER is the standalone conjunct
      * "derived column 0 IS NOT NULL", the atom GE INT64_MIN */
     for (size_t l = 0; l < s->lookups.size(); l++) {
         const cs_lookup &lk = s->lookups[l];
         s->cols_mask |= 1ull << lk.key_column;
+        s->need_mask |= 1ull << lk.key_column;
         if (!lk.inner) continue;
         cstripe_pred q{};
         q.column = lk.first_col;
@@ -1676,7 +1708,7 @@ extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t co
                          return a.or_group < b.or_group;
                      });
     if (s->cols_mask == 0)
-        s->cols_mask = 1;   /* pure count(*): still scan one column's chunks */
+        s->cols_mask = s->need_mask = 1;   /* pure count(*): still scan one column's chunks */
     /* chunk-refutation keys of the TEXT / VARTEXT set predicates */
     s->set_keys.resize(s->preds.size());
     bool any_set = false;
@@ -1790,6 +1822,26 @@ extern "C" cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t co
                         j++;
                         continue;
                     }
+                    if (cs_pred_is_like(p)) {
+                        /* LIKE: every match starts with the pattern's literal
+                         * prefix `pre`, so its key lies in [key(pre),
+                         * key(pre[:7] padded with 0xFF)]; NOT LIKE never refutes */
+                        const std::string &tc = s->text_consts[(size_t)p.ival];
+                        uint8_t pre[7];
+                        uint32_t np = 0;
+                        if (p.op == CSTRIPE_PRED_LIKE && nd.has_min_max)
+                            np = cslk_literal_prefix((const uint8_t *)tc.data(), (uint32_t)tc.size(), pre);
+                        bool refuted = false;
+                        if (np) {
+                            const int64_t klo = csvt_prefix_key(pre, np);
+                            for (uint32_t b = np; b < 7; b++) pre[b] = 0xFF;
+                            const int64_t khi = csvt_prefix_key(pre, 7);
+                            refuted = nd.max_i < klo || nd.min_i > khi;
+                        }
+                        if (!refuted) group_refuted = false;
+                        j++;
+                        continue;
+                    }
                     if (r->cols[p.column].type == CSTRIPE_VARTEXT) {
                         const std::string &tc = s->text_consts[(size_t)p.ival];
                         text_key = csvt_prefix_key((const uint8_t *)tc.data(), (uint32_t)tc.size());
@@ -1849,11 +1901,43 @@ extern "C" uint64_t cstripe_gpu_staged_bytes(const cstripe_scan *s)
     return s ? csgpu_staged_bytes(s) : 0;
 }
 
+extern "C" int cstripe_like_match(const uint8_t *pat, uint32_t plen, const uint8_t *val, uint32_t vlen)
+{
+    if ((!pat && plen) || (!val && vlen)) { cs_set_err("like_match: bad args"); return CSTRIPE_ERR_ARG; }
+    const int bad = cslk_check_pattern(pat, plen);
+    if (bad) {
+        cs_set_err(bad == 1 ? "like_match: pattern longer than CSTRIPE_LIKE_MAX_PATTERN" :
+                   bad == 2 ? "LIKE pattern must not end with escape character" :
+                              "like_match: pattern is not valid UTF-8");
+        return CSTRIPE_ERR_ARG;
+    }
+    return cslk_match(pat, plen, val, vlen);
+}
+
+extern "C" int cstripe_scan_last_like_ms(const cstripe_scan *s, double *match_ms, double *apply_ms)
+{
+    if (!s) return CSTRIPE_ERR_ARG;
+    if (match_ms) *match_ms = s->last_like_match_ms;
+    if (apply_ms) *apply_ms = s->last_like_apply_ms;
+    return CSTRIPE_OK;
+}
+
+extern "C" int cstripe_scan_like_form(const cstripe_scan *s, uint32_t column)
+{
+    if (!s || !s->gpu || column >= s->like_forms.size()) return CSTRIPE_LIKE_FORM_NONE;
+    return s->like_forms[column];
+}
+
 extern "C" int cstripe_scan_text_dict(const cstripe_scan *s, uint32_t col, uint32_t *n,
                                       const uint64_t **offsets, const uint8_t **bytes)
 {
     if (!s || !n || !offsets || !bytes) { cs_set_err("scan_text_dict: bad args"); return CSTRIPE_ERR_ARG; }
     if (!s->gpu) { cs_set_err("scan not staged — the text dictionary is built by cstripe_gpu_stage"); return CSTRIPE_ERR_NOGPU; }
+    if (cstripe_scan_like_form(s, col) == CSTRIPE_LIKE_FORM_STREAM) {
+        cs_set_err("scan_text_dict: column %u is only pattern-matched (LIKE stream form) and has "
+                   "no dictionary — add it to cols_mask", col);
+        return CSTRIPE_ERR_ARG;
+    }
     if (col >= s->text_dicts.size() || !s->text_dicts[col].built) {
         cs_set_err("scan_text_dict: column %u is not a projected VARTEXT column", col);
         return CSTRIPE_ERR_ARG;

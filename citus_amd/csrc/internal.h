@@ -110,6 +110,11 @@ struct cs_expr {
 struct cstripe_scan {
     cstripe_reader *r = nullptr;
     uint64_t cols_mask = 0;
+    /* the columns whose VALUES some surface may read: the caller's mask, the
+     * expressions' inputs, the lookups' keys and the columns of every
+     * predicate but LIKE / NOT LIKE. A VARTEXT column in cols_mask and not
+     * here is only pattern-matched (the stage's stream form). */
+    uint64_t need_mask = 0;
     std::vector<cstripe_pred> preds;
     std::vector<cs_lookup> lookups;
     uint32_t n_derived = 0;                 /* payload columns of all lookups */
@@ -129,6 +134,9 @@ struct cstripe_scan {
     double last_text_walk_ms = 0.0;
     double last_text_dict_ms = 0.0;
     double last_text_remap_ms = 0.0;
+    std::vector<uint8_t> like_forms;        /* [column]: CSTRIPE_LIKE_FORM_* at the last stage */
+    double last_like_match_ms = 0.0;        /* stage-time LIKE split */
+    double last_like_apply_ms = 0.0;
     std::vector<cs_selchunk> sel;     /* surviving chunk groups, scan order */
     int64_t chunk_groups_filtered = 0;
     cs_gpu_state *gpu = nullptr;
@@ -167,6 +175,10 @@ struct cstripe_scan {
 static inline uint32_t cs_scan_ncols(const cstripe_scan *s)
 {
     return s->r->head.column_count + s->n_derived + (uint32_t)s->exprs.size();
+}
+static inline bool cs_pred_is_like(const cstripe_pred &p)
+{
+    return p.op == CSTRIPE_PRED_LIKE || p.op == CSTRIPE_PRED_NOT_LIKE;
 }
 static inline bool cs_col_derived(const cstripe_scan *s, uint32_t c)
 {

@@ -210,12 +210,20 @@ void cstripe_default_options(cstripe_options *opts);
  * ScalarArrayOpExpr the reference pushes into the scan whole, at any list
  * length (columnar_customscan.c:840-850), and `col <> ALL(array)`. Their
  * ival is an INDEX into the value sets of cstripe_scan_begin_sets; one atom
- * whatever the set's size, so a long list does not eat CSTRIPE_MAX_PREDS. */
+ * whatever the set's size, so a long list does not eat CSTRIPE_MAX_PREDS.
+ *
+ * LIKE / NOT_LIKE are the pattern atoms over a VARTEXT column; their ival is
+ * an INDEX into the text constants of cstripe_scan_begin_ex, which holds the
+ * pattern (see "LIKE / NOT LIKE" below cstripe_scan_begin_ex). */
 typedef enum cstripe_predop {
     CSTRIPE_PRED_LT = 0, CSTRIPE_PRED_LE, CSTRIPE_PRED_GT, CSTRIPE_PRED_GE,
     CSTRIPE_PRED_EQ, CSTRIPE_PRED_NE,
     CSTRIPE_PRED_IN = 6, CSTRIPE_PRED_NOT_IN = 7,
+    CSTRIPE_PRED_LIKE = 8, CSTRIPE_PRED_NOT_LIKE = 9,
 } cstripe_predop;
+
+/* longest LIKE pattern, bytes */
+#define CSTRIPE_LIKE_MAX_PATTERN 256
 
 typedef struct cstripe_pred {
     uint32_t    column;    /* 0-indexed (reference uses 1-indexed attno) */
@@ -409,6 +417,77 @@ cstripe_scan *cstripe_scan_begin_ex(cstripe_reader *r, uint64_t cols_mask,
                                     const cstripe_pred *preds, uint32_t n_preds,
                                     const cstripe_text_const *text_consts,
                                     uint32_t n_text_consts);
+/* LIKE / NOT LIKE — CSTRIPE_PRED_LIKE / CSTRIPE_PRED_NOT_LIKE, accepted by
+ * cstripe_scan_begin_ex, _sets, _lookups and _exprs on a VARTEXT table
+ * column; ival indexes text_consts (the pattern), fval is ignored, or_group
+ * works as for every atom. Plain cstripe_scan_begin has no constants and
+ * fails.
+ *  - Pattern language: PG LIKE with the default escape under "C" collation in
+ *    a UTF-8 database. '%' matches any run of characters, none included; '_'
+ *    exactly one character; '\x' the byte x literally; any other byte itself.
+ *    A character is one byte plus the continuation bytes ((b & 0xC0) == 0x80)
+ *    that follow it. The match is anchored at both ends. x LIKE p passes iff
+ *    x is non-NULL and matches; x NOT LIKE p iff x is non-NULL and does not;
+ *    a NULL operand fails both.
+ *  - Exact for patterns and values that are valid UTF-8, pure ASCII included.
+ *    For a value that is not valid UTF-8 the verdict is unspecified (PG's
+ *    recursive matcher and this one differ on such bytes); it is still
+ *    deterministic, terminates, and reads nothing outside the value.
+ *  - Begin errors (NULL, the message names the predicate index): the column
+ *    is not VARTEXT (TEXT slots, derived and computed ids included); the
+ *    constant index is out of range; the pattern is longer than
+ *    CSTRIPE_LIKE_MAX_PATTERN; it ends in an unescaped backslash ("LIKE
+ *    pattern must not end with escape character"); it is not valid UTF-8.
+ *  - Chunk refutation (host): with `pre` the literal bytes before the first
+ *    unescaped '%' or '_', escapes resolved — LIKE refutes a chunk that has
+ *    min/max iff pre is non-empty and max_key < key(pre) or min_key >
+ *    key(pre[:7] padded with 0xFF to 7 bytes). NOT LIKE never refutes;
+ *    all-NULL chunks survive; an or_group refutes only if every member does.
+ *    The device prune kernel stays off, as for every VARTEXT predicate.
+ *  - Device evaluation, at cstripe_gpu_stage: each distinct (column, pattern
+ *    bytes) pair becomes one I8 membership column, laid out and counted
+ *    exactly like the member slot of an IN / NOT IN pair (one of the 16
+ *    projected slots; over the limit the stage returns CSTRIPE_ERR_ARG and
+ *    the scan stays unstaged). LIKE is member == 1, NOT LIKE member == 0;
+ *    both of one pattern share the slot. No query kernel knows about LIKE.
+ *  - Two read forms per column, chosen per stage (cstripe_scan_like_form).
+ *    DICT: the column also needs ranks — it is in the caller's cols_mask, or
+ *    carries any other predicate or set — so the dictionary is built as
+ *    usual, each of its n_dict entries is matched once, and one pass writes
+ *    member[i] = flag[slot of value i]. STREAM: the column is absent from the
+ *    caller's cols_mask and every predicate on it is LIKE / NOT LIKE —
+ *    decode, header walk, then one match per value straight off the walk's
+ *    (offset, length) words: no hash table, no gather, no host sort, no
+ *    ranks, and no CSTRIPE_VARTEXT_MAX_DISTINCT limit, so a near-unique
+ *    comment column can be filtered.
+ *  - A STREAM column has no values for anyone else: cstripe_scan_text_dict,
+ *    a wanted or order column of scan_select / scan_select_topn, a key of
+ *    scan_agg_hashed / scan_agg_hashed_topn and a COUNT_COL operand
+ *    return CSTRIPE_ERR_ARG with a message that names the column and says
+ *    "add it to cols_mask".
+ *  - CSTRIPE_LIKE_FORM=dict|stream (environment, read per stage) is a switch
+ *    for tests: `stream` on a column that needs ranks falls back to DICT,
+ *    `dict` always works and is subject to the distinct limit. Results never
+ *    depend on it.
+ *  - Out of scope: ILIKE, SIMILAR TO, regular expressions, a custom ESCAPE
+ *    character; LIKE on TEXT slots or inside expressions; LIKE-specific
+ *    handling in the device prune kernel; splitting long values across lanes
+ *    (one lane matches one value, so lanes diverge on value length);
+ *    collations other than "C". */
+/* The matcher itself, host only (no GPU needed): 1 when val[0..vlen) matches
+ * pat[0..plen), 0 when not, CSTRIPE_ERR_ARG for a pattern scan_begin would
+ * refuse. It runs the same source the device match kernel runs (like.h). */
+int cstripe_like_match(const uint8_t *pat, uint32_t plen, const uint8_t *val, uint32_t vlen);
+/* device milliseconds of the last cstripe_gpu_stage's LIKE work, all
+ * patterns together: the match kernels, and the DICT form's apply passes.
+ * Both 0 without a LIKE atom. Either out pointer may be NULL. */
+int cstripe_scan_last_like_ms(const cstripe_scan *s, double *match_ms, double *apply_ms);
+/* read form of table column `column` at the last stage: CSTRIPE_LIKE_FORM_NONE
+ * when the scan is unstaged or no LIKE atom names the column */
+#define CSTRIPE_LIKE_FORM_NONE   0
+#define CSTRIPE_LIKE_FORM_DICT   1
+#define CSTRIPE_LIKE_FORM_STREAM 2
+int cstripe_scan_like_form(const cstripe_scan *s, uint32_t column);
 /* scan_begin_sets: scan_begin_ex plus value sets for IN / NOT_IN atoms. With
  * n_sets == 0 it is exactly cstripe_scan_begin_ex (which calls it).
  *  - For op IN / NOT_IN, ival is an INDEX into sets — for every column type,
@@ -677,8 +756,9 @@ typedef struct cstripe_expr    { const cstripe_expr_op *ops; uint32_t n_ops; uin
  *    values; it then reads as an ordinary sparse I64 column in scratch. Such
  *    scans report CSTRIPE_AGG_PATH_GENERAL. A restage re-evaluates.
  *  - Out of scope: float / TEXT / VARTEXT operands or results, expressions
- *    over other expressions or over aggregates, LIKE, pruning through an
- *    expression, a dense result form, computed columns in next_batch /
+ *    over other expressions or over aggregates, LIKE as an expression op
+ *    (LIKE / NOT LIKE are predicates on a VARTEXT table column, accepted
+ *    here as by cstripe_scan_begin_ex), pruning through an expression, a dense result form, computed columns in next_batch /
  *    read_row. */
 cstripe_scan *cstripe_scan_begin_exprs(cstripe_reader *r, uint64_t cols_mask,
                                        const cstripe_pred *preds, uint32_t n_preds,
